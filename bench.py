@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark: Mpixels/s of the ImageEncoder encode hot path (DCT + quant + zig-zag RLE pack) on
-MI355X, with the reference's own OpenMP CPU encoder timed beside it.
+MI355X; with --full the reference's own OpenMP CPU encoder is timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the encoder over one batch of distinct synthetic frames resident in HBM
 (a rotating set larger than the 256 MiB Infinity Cache, so HBM is what is measured):
@@ -24,10 +24,24 @@ A "step" is one pass of the encoder over one batch of distinct synthetic frames 
 relays rank 0's line.  One process per GPU; value = all pixels encoded by all ranks / max-over-
 ranks wall time of the K timed steps (inputs already resident, outputs left in HBM).
 
-After the timed steps every run checks its own output (``bit_exact``): the reference golden md5
-of the 4K synthetic image (c2/c3/c5: image 0 of the batch is that golden's frame) or, for c4, the
-golden 3-frame 1080p gop=1 stream plus the assembled N-rank stream against a single-GPU encode of
-the same frames; asynchronous launches are checked for look-back timeouts (ie_sync).
+A plain run sets up, warms up, times the K steps and prints the result line (the headline figure,
+``ms_per_step`` and the configuration); asynchronous launches are checked for look-back timeouts
+(ie_sync).  --dump-outputs DIR also writes what the last timed step left in its output buffer (rank 0;
+the inputs are seeded, so the same arguments give the same files on every run):
+
+  DIR/end_bits.npy  float64 [rows]     the end bit of every stream (c2/c3: one row per image of the
+                                       batch; c5: 8 x its Huffman byte count; c4: the one stream)
+  DIR/streams.npy   float32 [rows, S]  the stream bytes at S fixed offsets of each row: the first
+                                       4096 bytes and a seeded stratified sample of the rest of the
+                                       row's capacity (rows x S = 8 Mi values), zero at and after
+                                       the stream's end
+
+--full adds everything else the line can carry, each measured in runs of its own after the timed
+steps: the roofline of the dominant kernel, the CPU baseline, the single-frame, host-buffer, decode
+and P-frame timings, the Huffman stage figures (c5) and the output self-check (``bit_exact``): the
+reference golden md5 of the 4K synthetic image (c2/c3/c5: image 0 of the batch is that golden's
+frame) or, for c4, the golden 3-frame 1080p gop=1 stream plus the assembled N-rank stream against a
+single-GPU encode of the same frames.  The --no-* options leave single legs out of a --full run.
 """
 from __future__ import annotations
 
@@ -69,6 +83,9 @@ WORKLOADS = {
     "c5": dict(w=3840, h=2160, n=4, matrix="matrix.txt", batch=16, resident=64, gen="U", huffman=True,
                golden="synU4k_4x4_huff"),
 }
+DUMP_VALUES = 8 << 20  # --dump-outputs: sampled stream bytes in all (32 MiB as float32)
+DUMP_HEAD = 4096  # ... of which the first bytes of every row, whole
+DUMP_SEED = 0x1E5EED
 METRIC = "Mpixels/s encode (DCT+quant+RLE), 4K grayscale, 1/2/4/8 GPU + CPU ref"
 ARITH = "FP32 separable DCT + FP64 re-evaluation of near-tie coefficients (bit-exact vs the FP64 reference)"
 
@@ -81,6 +98,11 @@ def parse():
     p.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                    help="default: c2 at one GPU, c4 (the multi-GPU configuration) above")
     p.add_argument("--mode", default="fast", choices=["fast", "exact"])
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's streams (a fixed seeded sample) and end bits as DIR/*.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check everything beside the headline figure (roofline, CPU baseline, "
+                        "single-frame / host-buffer / decode / P-frame / Huffman stage timings, output self-check)")
     p.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     p.add_argument("--cpu-iters", type=int, default=2)
     p.add_argument("--no-decode", action="store_true", help="skip the one-image decode timing (inverse path)")
@@ -177,6 +199,30 @@ def cpu_baseline(cfg, frame: np.ndarray) -> dict | None:
     return dict(value=round(w * h / (dt * 1e6), 3), unit="Mpx/s", cores=threads, kind="port",
                 sample=f"{iters} x {w}x{h} {cfg['gen']} frame, oracle restatement, {threads} threads",
                 reference_unavailable=why, host=info)
+
+
+def dump_outputs(torch, path: str, buf, rows: int, pitch: int, end_bits) -> None:
+    """--dump-outputs: ``buf`` holds ``rows`` streams at ``pitch`` bytes, row r ending at bit
+    ``end_bits[r]``.  The offsets sampled depend on rows and pitch alone (module docstring)."""
+    os.makedirs(path, exist_ok=True)
+    ends = np.asarray(end_bits, dtype=np.uint64).reshape(rows)
+    per_row = min(pitch, DUMP_VALUES // rows)
+    head = min(DUMP_HEAD, per_row)
+    k = per_row - head
+    off = np.arange(head, dtype=np.int64)
+    if k:  # one offset in each of k equal strata of the rest of the row
+        rng = np.random.default_rng(DUMP_SEED)
+        stride = (pitch - head) // k
+        off = np.concatenate([off, head + np.arange(k, dtype=np.int64) * stride + rng.integers(0, stride, k)])
+    got = buf[: rows * pitch].view(rows, pitch).index_select(1, torch.from_numpy(off).to(buf.device)).cpu().numpy()
+    # bytes past the end of a stream (and the bits past it in its last byte) are whatever an earlier
+    # step left there: not output
+    nbytes = ((ends + np.uint64(7)) // np.uint64(8)).astype(np.int64)[:, None]
+    keep = np.where(off[None, :] < nbytes - 1, 0xFF, 0).astype(np.uint8)
+    tail = ((0xFF00 >> ((ends.astype(np.int64) - 1) % 8 + 1)) & 0xFF).astype(np.uint8)[:, None]
+    keep = np.where(off[None, :] == nbytes - 1, tail, keep)
+    np.save(os.path.join(path, "end_bits.npy"), ends.astype(np.float64))
+    np.save(os.path.join(path, "streams.npy"), (got & keep).astype(np.float32))
 
 
 class Timer:
@@ -278,6 +324,10 @@ def main():
     timer = Timer(torch, dist, dev, stream, world)
     extra = {}
     check = {}
+    full = args.full
+    last_step = args.warmup + args.steps - 1
+    dump = args.dump_outputs if rank == 0 and args.steps > 0 else None
+    enc_s = fallbacks = None  # measured by --full only
 
     if wl in ("c2", "c3", "c5"):
         # resident synthetic frames, distinct per rank (seed offset), generated on the device;
@@ -295,12 +345,13 @@ def main():
             o.view(B, pitch)[:, : hdr.size].copy_(hdr_t)
         # sizes for the algorithmic byte count (deterministic per frame)
         ends_per_slot = []
-        for slot in range(nslots):
+        for slot in range(nslots if full else 0):
             ends_per_slot.append(codec.encode_images(frames[slot * B:(slot + 1) * B], w, h, outs[0],
                                                      out_pitch=pitch, nframes=B, start_bit=hdr_bits, mode=mode))
-        out_bytes_per_launch = sum(int(sum((int(e) - hdr_bits + 7) // 8 for e in ends))
-                                   for ends in ends_per_slot) / nslots
-        fallbacks = codec.last_fallbacks()
+        if full:
+            out_bytes_per_launch = sum(int(sum((int(e) - hdr_bits + 7) // 8 for e in ends))
+                                       for ends in ends_per_slot) / nslots
+            fallbacks = codec.last_fallbacks()
 
         if not cfg["huffman"]:
             def step(i):
@@ -335,11 +386,18 @@ def main():
                 pending.append((out, i % 2))
         wall, gpu_s = timer.run(step, args.warmup, args.steps, drain=drain)
         codec.sync()  # raises if any asynchronous launch of the timed region timed out
+        if dump:
+            if cfg["huffman"]:  # the drained step's Huffman streams and their byte counts
+                dump_outputs(torch, dump, houts, B, hpitch, [8 * int(x) for x in hsizes])
+            else:
+                ends_t = torch.zeros(B, dtype=torch.int64, device=dev)
+                codec.end_bits_into(ends_t, B)
+                dump_outputs(torch, dump, outs[last_step % len(outs)], B, pitch, ends_t.cpu().numpy())
         px_total = world * args.steps * B * w * h
         in_bytes_per_launch = B * w * h
         # dominant kernel alone: the block encoder's launch time on its stream
         enc_s = gpu_s / args.steps
-        if cfg["huffman"]:
+        if full and cfg["huffman"]:
             def enc_only(i):
                 slot = i % nslots
                 codec.encode_images(frames[slot * B:(slot + 1) * B], w, h, outs[i % len(outs)], out_pitch=pitch,
@@ -413,7 +471,7 @@ def main():
                                            "note": "Huffman stream read + symbols written per call, wall time incl. "
                                                    "its one host sync (device output: the emit is bounded by the "
                                                    "output size, then the total and flags are read back together)"}
-        if args.single_frame:  # one 4K frame per launch: the latency of the single-image configuration
+        if full and args.single_frame:  # one 4K frame per launch: the latency of the single-image configuration
             one = outs[0][:pitch]
 
             def single(i):
@@ -424,7 +482,7 @@ def main():
             extra["single_frame"] = {"us_per_frame": round(g1 / (4 * B) * 1e6, 2),
                                      "Mpx_s": round(w * h / (g1 / (4 * B)) / 1e6, 1)}
         codec.sync()
-        if not args.no_check and rank == 0:
+        if full and not args.no_check and rank == 0:
             # image 0 of slot 0 is the reference's golden 4K frame: its file md5
             g = golden(cfg["golden"])
             out = outs[0]
@@ -437,7 +495,7 @@ def main():
                 got = out[: (int(ends[0]) + 7) // 8].cpu().numpy().tobytes()
             check = {"golden": cfg["golden"], "md5": md5(got), "expected_md5": g["md5"],
                      "bit_exact": md5(got) == g["md5"] and len(got) == g["size"]}
-        if not cfg["huffman"] and not args.no_e2e:
+        if full and not cfg["huffman"] and not args.no_e2e:
             # end to end from HOST buffers (reported separately, never `value`): host frames
             # in, host streams out, through the streamed path (chunks in flight on three HIP
             # streams, PCIe full duplex).  Pageable numpy buffers go through the library's pinned
@@ -470,7 +528,7 @@ def main():
             extra["e2e_host_buffers"] = dict(e2e, note="host frames in, host streams out: streamed path (H2D, "
                                                        "encode, D2H of consecutive chunks concurrent); "
                                                        "PCIe-inclusive, never `value`")
-        if not cfg["huffman"] and not args.no_decode:
+        if full and not cfg["huffman"] and not args.no_decode:
             # the inverse path: one image's stream decoded back to pixels on the
             # device (chunked record walk + index scan + FP64 IDCT), wall time per call incl. syncs
             ends0 = codec.encode_images(frames[:B], w, h, outs[0], out_pitch=pitch, nframes=B, start_bit=hdr_bits,
@@ -494,7 +552,7 @@ def main():
                                          "path": f"exact parse: {chunks} chunk transfer tables composed in "
                                                  f"{groups} level(s), then count and decode launches; "
                                                  "one host sync at the end (device-resident stream and pixels)"}
-        if n == 4 and not cfg["huffman"] and not args.no_gop:
+        if full and n == 4 and not cfg["huffman"] and not args.no_gop:
             # P-frames: 8 resident frames as one video, gop = 1 against gop = 8
             # (one I-frame + 7 P-frames: macroblock search + coded error + reconstruction), merange 16
             F, mer = 8, 16
@@ -522,7 +580,7 @@ def main():
                     f"{' +Huffman' if cfg['huffman'] else ''}, batch of {B} independent images per step, "
                     f"{R} distinct resident frames per GPU ({R * w * h / 2**20:.0f} MiB)")
         parallelism = f"independent images sharded x{world} (no collective)"
-        cpu_frame = frames[0].cpu().numpy() if rank == 0 else None
+        cpu_frame = frames[0].cpu().numpy() if rank == 0 and full else None
     else:  # c4: one gop=1 video stream, frames sharded over ranks, RCCL gather to rank 0
         K = args.chunks or cfg["chunks"] or (1 if world == 1 else 2)
         m = max(B // K, 1)  # frames per rank per chunk
@@ -558,6 +616,8 @@ def main():
             wall, _ = timer.run(G.step, args.warmup, args.steps)
             total_bits = G.total
             segs = G.segs
+            if dump:
+                dump_outputs(torch, dump, G.out, 1, root_cap, [G.total])
         else:  # one GPU: the whole batch in one launch straight after the header (nothing to gather)
             out_root = torch.zeros(root_cap, dtype=torch.uint8, device=dev)
             out_root[: hdr.size].copy_(torch.from_numpy(hdr).to(dev))
@@ -565,52 +625,58 @@ def main():
             wall, _ = timer.run(lambda i: codec.encode_frames(frames[i % nsets].view(nloc, h, w), w, h, out_root,
                                                               start_bit=hb, nframes=nloc, mode=mode,
                                                               want_sizes=False), args.warmup, args.steps)
-            total_bits = codec.encode_frames(frames[0], w, h, out_root, start_bit=hb, nframes=nloc, mode=mode)[1]
+            if dump:
+                end_t = torch.zeros(1, dtype=torch.int64, device=dev)
+                codec.end_bits_into(end_t)
+                dump_outputs(torch, dump, out_root, 1, root_cap, end_t.cpu().numpy())
+            if full:
+                total_bits = codec.encode_frames(frames[0], w, h, out_root, start_bit=hb, nframes=nloc, mode=mode)[1]
         codec.sync()
         shifter.sync()
-        # the encoder launches alone (no gather): the dominant kernel's time
-        def enc_only(i):
-            for k in range(K):
-                codec.encode_frames(frames[i % nsets, k * m:(k + 1) * m], w, h, segs[k], start_bit=0, nframes=m,
-                                    mode=mode, want_sizes=False)
-        wall_enc, gpu_enc = timer.run(enc_only, 1, args.steps)
-        codec.sync()
         px_total = world * args.steps * nloc * w * h
-        extra["encode_only_Mpx_s"] = round(px_total / wall_enc / 1e6, 2)
-        extra["stream_bytes"] = (total_bits + 7) // 8
-        extra["world_size_backend"] = {"world": dist.get_world_size() if world > 1 else 1,
-                                       "backend": dist.get_backend() if world > 1 else None}
-        in_bytes_per_launch = m * w * h
-        out_bytes_per_launch = extra["stream_bytes"] / (world * K)
-        enc_s = gpu_enc / (args.steps * K)
-        fallbacks = codec.last_fallbacks()
-        if not args.no_check:
-            ok = True
-            if world > 1:
-                # the assembled stream of the last step vs ONE device encoding the same F frames
-                last = (args.warmup + args.steps - 1) % nsets
-                G.step(last)
-                torch.cuda.synchronize(dev)
+        if full:
+            # the encoder launches alone (no gather): the dominant kernel's time
+            def enc_only(i):
+                for k in range(K):
+                    codec.encode_frames(frames[i % nsets, k * m:(k + 1) * m], w, h, segs[k], start_bit=0, nframes=m,
+                                        mode=mode, want_sizes=False)
+            wall_enc, gpu_enc = timer.run(enc_only, 1, args.steps)
+            codec.sync()
+            extra["encode_only_Mpx_s"] = round(px_total / wall_enc / 1e6, 2)
+            extra["stream_bytes"] = (total_bits + 7) // 8
+            extra["world_size_backend"] = {"world": dist.get_world_size() if world > 1 else 1,
+                                           "backend": dist.get_backend() if world > 1 else None}
+            in_bytes_per_launch = m * w * h
+            out_bytes_per_launch = extra["stream_bytes"] / (world * K)
+            enc_s = gpu_enc / (args.steps * K)
+            fallbacks = codec.last_fallbacks()
+            if not args.no_check:
+                ok = True
+                if world > 1:
+                    # the assembled stream of the last step vs ONE device encoding the same F frames
+                    last = (args.warmup + args.steps - 1) % nsets
+                    G.step(last)
+                    torch.cuda.synchronize(dev)
+                    if rank == 0:
+                        allf = synth.uniform_device(w, h, F, synth.DEFAULT_SEED + last * F, dev, torch)
+                        ref = torch.zeros(root_cap, dtype=torch.uint8, device=dev)
+                        ref[: hdr.size].copy_(torch.from_numpy(hdr).to(dev))
+                        _, end = codec.encode_frames(allf, w, h, ref, start_bit=hb, nframes=F, mode=mode)
+                        nbytes = (end + 7) // 8
+                        ok = end == G.total and torch.equal(ref[:nbytes], G.out[:nbytes])
+                        check["gathered_equals_single_gpu"] = bool(ok)
+                        del allf, ref
                 if rank == 0:
-                    allf = synth.uniform_device(w, h, F, synth.DEFAULT_SEED + last * F, dev, torch)
-                    ref = torch.zeros(root_cap, dtype=torch.uint8, device=dev)
-                    ref[: hdr.size].copy_(torch.from_numpy(hdr).to(dev))
-                    _, end = codec.encode_frames(allf, w, h, ref, start_bit=hb, nframes=F, mode=mode)
-                    nbytes = (end + 7) // 8
-                    ok = end == G.total and torch.equal(ref[:nbytes], G.out[:nbytes])
-                    check["gathered_equals_single_gpu"] = bool(ok)
-                    del allf, ref
-            if rank == 0:
-                # the golden gop=1 stream (3 x 1080p YUV420 frames) through the same encoder
-                g = golden(cfg["golden"])
-                gy = torch.from_numpy(synth.frames("U", w, h, 3, seed=g["input"]["seed"])).to(dev)
-                ghdr, ghb = write_header(n, q, True, w, h, video=True, frames=3, gop=1, merange=16)
-                gout = torch.zeros(stream_bound(w, h, n, 3, ghb) + 64, dtype=torch.uint8, device=dev)
-                gout[: ghdr.size].copy_(torch.from_numpy(ghdr).to(dev))
-                _, gend = codec.encode_frames(gy, w, h, gout, start_bit=ghb, nframes=3, mode=mode)
-                got = gout[: (gend + 7) // 8].cpu().numpy().tobytes()
-                check.update({"golden": cfg["golden"], "md5": md5(got), "expected_md5": g["md5"]})
-                check["bit_exact"] = bool(ok and md5(got) == g["md5"])
+                    # the golden gop=1 stream (3 x 1080p YUV420 frames) through the same encoder
+                    g = golden(cfg["golden"])
+                    gy = torch.from_numpy(synth.frames("U", w, h, 3, seed=g["input"]["seed"])).to(dev)
+                    ghdr, ghb = write_header(n, q, True, w, h, video=True, frames=3, gop=1, merange=16)
+                    gout = torch.zeros(stream_bound(w, h, n, 3, ghb) + 64, dtype=torch.uint8, device=dev)
+                    gout[: ghdr.size].copy_(torch.from_numpy(ghdr).to(dev))
+                    _, gend = codec.encode_frames(gy, w, h, gout, start_bit=ghb, nframes=3, mode=mode)
+                    got = gout[: (gend + 7) // 8].cpu().numpy().tobytes()
+                    check.update({"golden": cfg["golden"], "md5": md5(got), "expected_md5": g["md5"]})
+                    check["bit_exact"] = bool(ok and md5(got) == g["md5"])
         B = nloc
         if world > 1:
             workload = (f"c4: {F} x {w}x{h} gop=1 video ({nloc} frames per GPU in {K} sub-batches of {m}), "
@@ -622,21 +688,15 @@ def main():
                         f"in {'one launch' if K == 1 else f'{K} launches'} on one GPU (nothing to gather)")
         parallelism = (f"frame-sharded x{world} + {'RCCL' if not gloo else 'gloo (rehearsal)'} gather" if world > 1
                        else "one GPU, whole batch in one launch (no collective)")
-        cpu_frame = frames[0, 0].cpu().numpy() if rank == 0 else None
+        cpu_frame = frames[0, 0].cpu().numpy() if rank == 0 and full else None
 
     value = px_total / wall / 1e6
-    alg_bytes = in_bytes_per_launch + out_bytes_per_launch
-    achieved = alg_bytes / enc_s / 1e9
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(cfg, cpu_frame)
 
     if rank == 0:
-        traffic = None
-        tf = os.path.join(ROOT, "profiles", f"{ROUND}_traffic_{wl}.json")  # this round's passes only
-        if os.path.exists(tf):
-            traffic = json.load(open(tf)).get("hbm_bytes_per_launch")
         line = {
             "metric": METRIC,
             "value": round(value, 2),
@@ -652,7 +712,17 @@ def main():
             "data": "synthetic (splitmix64 uniform 8-bit frames, seeded per rank)",
             "config": {"workload": workload, "block": n, "frames_per_step_per_gpu": B, "mode": args.mode,
                        "parallelism": parallelism},
-            "roofline": {
+            "arith": ARITH,
+            "full": full,
+        }
+        if full:
+            alg_bytes = in_bytes_per_launch + out_bytes_per_launch
+            achieved = alg_bytes / enc_s / 1e9
+            traffic = None
+            tf = os.path.join(ROOT, "profiles", f"{ROUND}_traffic_{wl}.json")  # this round's passes only
+            if os.path.exists(tf):
+                traffic = json.load(open(tf)).get("hbm_bytes_per_launch")
+            line["roofline"] = {
                 "bound": "hbm",
                 "achieved": round(achieved, 1),
                 "peak": HBM_PEAK_GBS,
@@ -664,14 +734,10 @@ def main():
                 "alg_bytes_per_launch": int(alg_bytes),
                 "launch_us": round(enc_s * 1e6, 2),
                 "read_only_frac": round(in_bytes_per_launch / enc_s / 1e9 / HBM_PEAK_GBS, 4),
-            },
-            "cpu_baseline": cpu,
-            "bit_exact": check.get("bit_exact"),
-            "check": check,
-            "fallback_coefs_per_launch": fallbacks,
-            "arith": ARITH,
-        }
-        line.update(extra)
+            }
+            line.update({"cpu_baseline": cpu, "bit_exact": check.get("bit_exact"), "check": check,
+                         "fallback_coefs_per_launch": fallbacks})
+            line.update(extra)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -11,5 +11,5 @@ for n in 4 8; do
   cp $(find $O/t$n -name "*kernel_stats.csv" | head -1) $O/${ROUND:-r05}_dec${n}_kernel_stats.csv
   python3 $R/tools/trace_grid.py $(find $O/t$n -name "*kernel_trace.csv" | head -1) rec_ || exit 1
 done
-timeout -k 10 300 python3 $R/bench.py --workload c3 --steps 3 --warmup 1 --no-cpu --no-e2e --no-gop --no-single-frame > $O/c3.json 2> $O/c3.err || exit 1
+timeout -k 10 300 python3 $R/bench.py --full --workload c3 --steps 3 --warmup 1 --no-cpu --no-e2e --no-gop --no-single-frame > $O/c3.json 2> $O/c3.err || exit 1
 python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('c3 bench decode', d['decode_one_image'])" $O/c3.json

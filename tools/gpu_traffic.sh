@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 ROUND=${ROUND:-r06}
 O=$R/gpurun_out/traffic; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-BOPT="--steps 6 --warmup 1 --no-cpu --no-single-frame --no-e2e --no-decode --no-gop --no-check"
+BOPT="--full --steps 6 --warmup 1 --no-cpu --no-single-frame --no-e2e --no-decode --no-gop --no-check"
 for wl in ${WLS:-c2 c3 c4 c5}; do
   case $wl in
     c3) K=encode_kernel; G="";;
