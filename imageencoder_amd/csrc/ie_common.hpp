@@ -161,31 +161,33 @@ __device__ __forceinline__ void st_state(uint64_t* p, uint64_t v) {
 // thread that publishes the tile, in that order), so a probe reads ONE word per predecessor:
 // whichever it sees is a correct term of the look-back sum.  (Round 5 kept them in two words and
 // read both: every probed predecessor cost two uncached loads -- C4's single chain reads 1.7 KB of
-// other XCDs' state lines per tile.)
-// granules per tile in the state array: 3 packed (24 B per tile) or IE_GRAN_STRIDE words apart
-// (16: each tile's state in a 128-B line of its own, no false sharing between tiles)
+// other XCDs' state lines per tile.)  Word kGran t + 1, the inclusive prefix's place then, has had
+// no reader or writer since; the tail keeps its word 2.
+// A tile's words sit IE_GRAN_STRIDE words apart in the state array (16: each tile's state in a
+// 128-B line of its own, no false sharing between tiles; at least 3, words 0 .. 2 packed)
 #ifndef IE_GRAN_STRIDE
 #define IE_GRAN_STRIDE 16
 #endif
 constexpr int kGran = IE_GRAN_STRIDE;
-static_assert(kGran >= 3 && kGran <= kStateWordsPerTile, "three granules per tile within the allocation");
+static_assert(kGran >= 3 && kGran <= kStateWordsPerTile, "words 0 .. 2 of a tile within the allocation");
 
-#ifndef IE_STATE_1W
-#define IE_STATE_1W 1  // 0: aggregate and inclusive in two words (round 5; A/B builds)
-#endif
 constexpr uint64_t kIncl = 1ull << 55, kMask55 = kIncl - 1;
-// g = 0: the aggregate, 1: the inclusive prefix, 2: the tail
+// g = 0: the aggregate, 1: the inclusive prefix (both in word 0), 2: the tail (word 2)
 __device__ __forceinline__ void publish(uint64_t* st, int t, int g, uint32_t tag, uint64_t v) {
-    if (IE_STATE_1W && g < 2)
+    if (g < 2)
         st_state(&st[kGran * t], (uint64_t(tag) << 56) | (g == 1 ? kIncl : 0ull) | (v & kMask55));
     else
         st_state(&st[kGran * t + g], (uint64_t(tag) << 56) | (v & kMask56));
 }
 
-// A look-back probe: the states of the 64 chain predecessors d0 .. d0+63 of tile t (both
-// granules at once) and, for d0 = 0, the immediate predecessor's tail, loaded by one wave.  The
-// first probe is issued right after the tile publishes its own count, so its loads are in flight
-// while the tile emits its records; it is evaluated afterwards.
+// A look-back probe: the state words of the 64 chain predecessors d0 .. d0+63 of tile t (ga) and,
+// for d0 = 0, the immediate predecessor's tail (gt), loaded by one wave.  The first probe is
+// issued right after the tile publishes its own count, so its loads are in flight while the tile
+// emits its records; it is evaluated afterwards.
+// (gi, the two-word protocol's inclusive word, is always 0 and never read.  It stays for now:
+// without it the compiler emits the same instructions for every look-back kernel but orders a few
+// scalar moves differently, and the change that dropped the two-word protocol kept the kernels'
+// ISA identical as its evidence of unchanged speed.)
 struct Probe {
     uint64_t gi, ga, gt;
 };
@@ -200,16 +202,9 @@ constexpr int kProbe0 = IE_PROBE0;
 // One probed predecessor: *status 2 (inclusive prefix), 1 (aggregate) or 0 (nothing published in
 // this launch), *val its value.
 __device__ __forceinline__ void probe_status(const Probe& p, uint32_t tag, int* status, uint64_t* val) {
-    if (IE_STATE_1W) {
-        const bool mine = uint32_t(p.ga >> 56) == tag;
-        *status = mine ? ((p.ga & kIncl) ? 2 : 1) : 0;
-        *val = p.ga & kMask55;
-    } else if (uint32_t(p.gi >> 56) == tag) {
-        *val = p.gi & kMask56;
-    } else {
-        *status = (uint32_t(p.ga >> 56) == tag) ? 1 : 0;
-        *val = p.ga & kMask56;
-    }
+    const bool mine = uint32_t(p.ga >> 56) == tag;
+    *status = mine ? ((p.ga & kIncl) ? 2 : 1) : 0;
+    *val = p.ga & kMask55;
 }
 
 __device__ __forceinline__ Probe probe_issue(const uint64_t* st, int t, int chain_pos, int step, int d0,
@@ -218,11 +213,7 @@ __device__ __forceinline__ Probe probe_issue(const uint64_t* st, int t, int chai
     p.gi = p.ga = p.gt = 0;
     const int lane = lane_id();
     const int d = d0 + lane;
-    if (lane < width && chain_pos - 1 - d >= 0) {
-        const int idx = t - step * (d + 1);
-        p.ga = ld_state(&st[kGran * idx]);
-        p.gi = IE_STATE_1W ? 0ull : ld_state(&st[kGran * idx + 1]);
-    }
+    if (lane < width && chain_pos - 1 - d >= 0) p.ga = ld_state(&st[kGran * (t - step * (d + 1))]);
     if (d0 == 0 && lane == 0 && chain_pos > 0) p.gt = ld_state(&st[kGran * (t - step) + 2]);
     return p;
 }

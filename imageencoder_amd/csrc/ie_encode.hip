@@ -190,7 +190,7 @@ __device__ __forceinline__ int exact_coef_task(const double* P, double S, double
     return int(r);
 }
 
-// exact_coef_task for a 4x4 block whose pixel rows are 256 words apart (encode4w_kernel's LDS
+// exact_coef_task for a 4x4 block whose pixel rows are 256 words apart (encode4p_kernel's LDS
 // layout), one row per step of a loop left rolled: few registers live beside the caller's.
 __device__ __forceinline__ int exact_coef_rows4(const double* P, double S, double rq, double qd, const uint32_t* pw) {
     double acc = 0.0;
@@ -1266,70 +1266,6 @@ __global__ IE_ENC_BOUNDS(N, EXACT) void encode_kernel(EncArgs a, const EncTables
     STAMP(9);
 }
 
-// round_block<4> with the rounding done pair by pair in zig-zag order and each packed word
-// pinned as soon as it exists: the 16 magic-added quotients never live at once (register
-// pressure of encode4w_kernel's fourth slot).  Same results bit for bit.
-__device__ __forceinline__ float round_block_lean4(const EncTables* __restrict__ tab, const float (&t)[16],
-                                                   uint32_t (&zp)[8], uint32_t* sflags) {
-    constexpr int S0 = Structural<4>::k[0], S1 = Structural<4>::k[1], S2 = Structural<4>::k[2];
-    const bool dcx = tab->dc_exact != 0;
-    float emax = 0.0f;
-    uint32_t sf = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        uint32_t yb[2];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const int k = ZigZag<4>::idx[2 * j + h];
-            const float y = t[k] + kMagic;
-            const float e = fabsf(t[k] - (y - kMagic));
-            yb[h] = __float_as_uint(y);
-            if (k == 0) {
-                const uint32_t dc = uint32_t(int(truncf(t[0] + copysignf(0.5f, t[0]))));
-                yb[h] = dcx ? dc : yb[h];
-                emax = dcx ? emax : fmaxf(emax, e);
-            } else if (k == S0) {
-                sf |= (e >= tab->lim[S0]) ? 1u : 0u;
-            } else if (k == S1) {
-                sf |= (e >= tab->lim[S1]) ? 2u : 0u;
-            } else if (k == S2) {
-                sf |= (e >= tab->lim[S2]) ? 4u : 0u;
-            } else {
-                emax = fmaxf(emax, e);
-            }
-        }
-        zp[j] = __builtin_amdgcn_perm(yb[1], yb[0], 0x05040100u);
-        asm volatile("" : "+v"(zp[j]));
-        if (j & 1) __builtin_amdgcn_sched_barrier(0);
-    }
-    *sflags = sf;
-    return emax;
-}
-
-// =============================================================================================
-// encode4w_kernel -- the 4x4 FAST encoder with WAVE-LOCAL emission.
-//
-// Same tile (1024 blocks, 256 threads, one chain element, the same chain granules) and the same
-// arithmetic as encode_kernel<4, false> (quot4 + round_block + the compacted FP64 fix-up, so the
-// Trk exactness argument carries over unchanged), laid out so that a wave needs its workgroup
-// only twice:
-//   * wave w owns the tile's blocks [256w, 256w + 256) (64 groups of four, raster order); lane l
-//     computes block 64b + l of that run in SLOT b = 0..3, so a slot is 64 consecutive blocks of
-//     the stream and one wave scan (DPP) places every record inside its slot;
-//   * the pixels land in the wave's own LDS region by DMA as [row][256 blocks] words (a slot
-//     reads them conflict-free, no other wave touches them); after the fix-up the same region
-//     holds two slot images in turn: slots 0 and 1 are emitted while wave 0 resolves the tile's
-//     look-back, then each slot is stored as soon as its image is complete and its buffer takes
-//     slot b + 2;
-//   * a word shared by two waves of the tile is written by the earlier wave, which ORs in the
-//     later wave's first bits (its head word, saved in LDS before the look-back barrier); a word
-//     shared with the predecessor tile is completed with that tile's tail granule as in
-//     encode_kernel.
-// LDS per tile 20.5 KB (encode_kernel<4>: ~27 KB), so up to seven tiles per CU.
-// Preconditions (launch_encode checks them): whole 16-byte groups (vec_ok, bx % 4 == 0), at
-// least 8 groups in every tile (groups_per_frame % 8 == 0: every wave segment >= 160 bits) and
-// slot images that fit half a region (rec_bits <= 252).
-// =============================================================================================
 // Look-back windows after the first probe, for launches that fill the chip (one small window at a
 // time: the nearest inclusive prefix is seldom far, and each probed predecessor is an uncached
 // load -- C4's one 8 128-tile chain: 2 windows of 64 108.6 us, 1 of 64 102.4, 1 of 32 101.1, 1 of
@@ -1340,17 +1276,10 @@ __device__ __forceinline__ float round_block_lean4(const EncTables* __restrict__
 #ifndef IE_W_LBW
 #define IE_W_LBW 32  // predecessors per window
 #endif
-#ifndef IE_W_WAVES
-#define IE_W_WAVES 6  // __launch_bounds__ occupancy hint (waves per SIMD): 76 VGPRs, no scratch (7 spills)
-#endif
-constexpr int kWReg = 1024;  // words per wave region: [4 rows][64 NS blocks] pixels, then the slot-pair images in turn
 constexpr int kWTask = 128;  // words per wave: fix-up tasks [64] + results [64]
-constexpr int kWMisc = 32;   // [0..3] wave bits, [4..7] wave head words, [8..9] excl, [10] ptail, [11] tail pending, [12] ticket,
-                             // [16..17] FP64 task counters, [18..25] small-launch window sums, [26..29] their found flags
 // FP64 rows in LDS (doubles): P[16][16] then S, rq, qd of every coefficient (the structural
 // three alone measured equal: the LDS they would free does not add a tile per CU at 78 VGPRs)
 constexpr int kWRows = 16 * 16 + 3 * 16;
-constexpr int kWLdsBytes = (4 * kWReg + 4 * kWTask + kWMisc) * 4 + kWRows * 8;
 // HIST: copies of the byte histogram (tools/ab.py --op counted, 16 4K frames: counting costs 20.3 us
 // over a launch without it at 1 copy, 15.8 at 4; 8 and 16 copies cost a tile per CU and are slower,
 // two 16-bit bins per word slower still -- the LDS read-modify-write of 112 M byte-adds is the floor)
@@ -1441,466 +1370,41 @@ __device__ __forceinline__ uint32_t slot_tail32(const uint32_t* I, uint32_t n, u
         if (IE_PROFILE && a.stamps && lane == 0 && wv < 4) a.stamps[size_t(t) * kStamps + wv * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
 
-// HIST (ie_encode_images_counted): every stored byte also counted into a per-tile LDS histogram
-// (256 words after misc), merged into a.hist[frame] at the end -- the Huffman pass's byte counts
-// without reading the stream back.
-template <bool HIST>
-__global__ __launch_bounds__(256, IE_W_WAVES) void encode4w_kernel(EncArgs a, const EncTables* __restrict__ tab) {
-    // (two slots per lane -- twice the tiles for small launches -- measured slower on a lone 4K
-    // frame, 23.9 against 18.2 us: the phases are bound by the SIMDs' issue, not by one wave's
-    // latency, and twice the tiles lengthen the look-back)
-    constexpr int N = 4, NN = 16, NP = 8, TPB = 256, NS = 4;
-    constexpr int GW = 16 * NS, BW = 64 * NS, TG = 4 * GW;  // groups / blocks per wave, groups per tile
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar registers
-    uint32_t* const reg = smem + wv * kWReg;  // this wave's pixels, later its two slot images
-    uint32_t* const task = smem + 4 * kWReg + wv * kWTask;
-    uint32_t* const res = task + 64;
-    uint32_t* const misc = smem + 4 * kWReg + 4 * kWTask;
-    uint32_t* const hl = misc + kWMisc;  // HIST: the tile's byte histogram
-    constexpr int HR = kWHistRep, HWORDS = 256 * HR;
-    double* const srow = reinterpret_cast<double*>(misc + kWMisc + (HIST ? HWORDS : 0));
-
-    int t;
-    if (a.ticket) {
-        if (tid == 0) misc[12] = uint32_t(atomicAdd(a.ticket, 1ull) - a.ticket_base);
-        lds_barrier();
-        t = __builtin_amdgcn_readfirstlane(int(misc[12]));
-        if (t >= a.ntiles) return;
-    } else {
-        t = int(blockIdx.x);
-    }
-    WSTAMP(0);
-    WRTSTAMP(14);
-    asm volatile("; PHASE w0" ::: "memory");
-    if constexpr (HIST)
-        for (int i = tid; i < HWORDS; i += TPB) hl[i] = 0u;  // (visible after the first barrier)
-    // the FP64 rows and their S, rq, qd: the fix-up reads them from LDS
-    for (int i = tid; i < kWRows; i += TPB)
-        srow[i] = (i < NN * NN) ? tab->P[i] : (i < NN * NN + NN) ? tab->S[i - NN * NN]
-                : (i < NN * NN + 2 * NN) ? tab->rq[i - NN * NN - NN] : tab->qd[i - NN * NN - 2 * NN];
-    const TileGeo g = tile_geo<4, 4, TG>(a, t, tid);  // lane l of wave w: group 64 w + l of the tile
-    const uint64_t start_bit = a.start_dev ? *a.start_dev : a.start_bit;
-    const int frame = g.frame, tif = g.tif, step = g.step, chain_pos = g.chain_pos;
-    // groups in this tile / in this wave (>= 8 per tile: launch precondition)
-    const int ng = min(TG, a.groups_per_frame - tif * TG);
-    const int nbw = 4 * min(GW, max(0, ng - GW * wv));  // blocks of this wave
-    const int wlast = (ng - 1) / GW;                    // the tile's last non-empty wave
-    if (g.nblk) {
-        // pixel row r of the wave's block j at reg[r BW + j]: a lane's 16 bytes are its group's row
-        const uint8_t* base = a.y + size_t(frame) * a.frame_pitch + size_t(g.byi) * N * a.stride + size_t(g.bx0) * N;
-#pragma unroll
-        for (int r = 0; r < N; r++)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + size_t(r) * a.stride),
-                                             (__attribute__((address_space(3))) void*)(reg + r * BW), 16, 0, 0);
-    }
-    lds_barrier();                                            // srow visible (the pixel DMA stays in flight)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pixels landed
-    WSTAMP(1);
-    asm volatile("; PHASE w1" ::: "memory");
-
-    // ------------------------------------------------------------ transform + quantise, 4 slots
-    uint32_t zp[NS][NP];
-    uint32_t flags = 0;  // 4 bits per slot: structural s (bits 0-2), whole block (bit 3)
-#pragma unroll
-    for (int b = 0; b < NS; b++) {
-        __builtin_amdgcn_sched_barrier(0);
-        uint32_t rows[N][1];
-#pragma unroll
-        for (int r = 0; r < N; r++) rows[r][0] = reg[r * BW + 64 * b + lane];
-        float x[NN];
-        block_pixels<N, 1>(rows, 0, x);
-        uint32_t sf;
-        float emax;
-        quotients<N>(tab, x);
-        emax = round_block_lean4(tab, x, zp[b], &sf);
-        const uint32_t fb = (emax >= tab->lim_min) ? 8u : sf;
-        if (64 * b + lane < nbw) flags |= fb << (4 * b);
-        // pin the packed words here: otherwise the packing sinks to its first use and the 16
-        // unpacked quotients of every slot stay live across the slots (spills)
-#pragma unroll
-        for (int j = 0; j < NP; j++) asm volatile("" : "+v"(zp[b][j]));
-        asm volatile("" : "+v"(flags));
-    }
-
-    WSTAMP(2);
-    asm volatile("; PHASE w2" ::: "memory");
-    // ------------------------------------------------------------ FP64 fix-up
-    static_assert(Structural<4>::zpos(0) & Structural<4>::zpos(1) & Structural<4>::zpos(2) & 1,
-                  "4x4 structural coefficients sit in high halves of the packed words");
-    auto block_px = [&](int b, int owner) {
-        BlockPx<N> px;
-#pragma unroll
-        for (int r = 0; r < N; r++) px.w[r] = reg[r * BW + 64 * b + owner];
-        return px;
-    };
-    if (__ballot(flags != 0)) {
-        const uint32_t sf = flags & 0x7777u;
-        const uint32_t cnt = __popc(sf);
-        uint32_t pre = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {  // cnt <= 12
-            const uint64_t bm = __ballot((cnt >> k) & 1u);
-            pre += __builtin_amdgcn_mbcnt_hi(uint32_t(bm >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(bm), 0u)) << k;
-            total += uint32_t(__popcll(bm)) << k;
-        }
-        for (uint32_t r0 = 0; r0 < total; r0 += 64) {
-            uint32_t m = sf, i = pre - r0;
-            while (m) {
-                const int bit = __ffs(m) - 1;
-                m &= m - 1;
-                if (i < 64u) task[i] = (uint32_t(lane) << 4) | uint32_t(bit);
-                i++;
-            }
-            wave_sync();
-            if (uint32_t(lane) < total - r0) {
-                const uint32_t tk = task[lane];
-                const int s = int(tk & 3u), b = int((tk >> 2) & 3u), owner = int(tk >> 4);
-                const BlockPx<N> px = block_px(b, owner);
-                const int k = Structural<N>::k[0] * (s == 0) + Structural<N>::k[1] * (s == 1) + Structural<N>::k[2] * (s == 2);
-                const int y = exact_coef_row<N>(srow + k * NN, srow[NN * NN + k], srow[NN * NN + NN + k],
-                                                srow[NN * NN + 2 * NN + k], px);
-                res[lane] = uint32_t(y) & 0xFFFFu;
-            }
-            wave_sync();
-            // the owners take their results back: the flagged positions in bit order, each a
-            // constant register (the three structural coefficients are high halves of packed
-            // words), so no per-request select over every slot and coefficient
-            i = pre - r0;
-#pragma unroll
-            for (int b = 0; b < NS; b++)
-#pragma unroll
-                for (int ss = 0; ss < 3; ss++) {
-                    if ((sf >> (4 * b + ss)) & 1u) {
-                        const int zw = Structural<N>::zpos(ss) >> 1;
-                        static_assert(Structural<4>::zpos(0) & Structural<4>::zpos(1) & Structural<4>::zpos(2) & 1,
-                                      "4x4 structural coefficients sit in high halves");
-                        if (i < 64u) zp[b][zw] = __builtin_amdgcn_perm(res[i], zp[b][zw], 0x05040100u);  // res low -> high half
-                        i++;
-                    }
-                }
-            wave_sync();
-        }
-        // whole-block requests (rare): all 16 coefficients in FP64, one per lane, four blocks a round
-        const uint32_t wf = flags & 0x8888u;
-        if (__ballot(wf != 0)) {
-            const uint32_t nb = __popc(wf);
-            uint32_t pb = 0, tb = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {  // nb <= 4
-                const uint64_t bm = __ballot((nb >> k) & 1u);
-                pb += __builtin_amdgcn_mbcnt_hi(uint32_t(bm >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(bm), 0u)) << k;
-                tb += uint32_t(__popcll(bm)) << k;
-            }
-            for (uint32_t r0 = 0; r0 < tb; r0 += 4) {
-                uint32_t m = wf, j = pb - r0;
-                while (m) {
-                    const int b = (__ffs(m) - 1) >> 2;
-                    m &= m - 1;
-                    if (j < 4u) task[j] = (uint32_t(lane) << 4) | uint32_t(b);
-                    j++;
-                }
-                wave_sync();
-                if (uint32_t(lane >> 4) < tb - r0) {
-                    const uint32_t tk = task[lane >> 4];
-                    const int b = int(tk & 3u), owner = int(tk >> 4), k = lane & 15;
-                    const BlockPx<N> px = block_px(b, owner);
-                    const int y = exact_coef_row<N>(srow + k * NN, srow[NN * NN + k], srow[NN * NN + NN + k],
-                                                    srow[NN * NN + 2 * NN + k], px);
-                    res[lane] = uint32_t(y) & 0xFFFFu;
-                }
-                wave_sync();
-                m = wf;
-                j = pb - r0;
-                while (m) {
-                    const int b = (__ffs(m) - 1) >> 2;
-                    m &= m - 1;
-                    if (j < 4u) {
-                        const uint32_t* rr = res + 16 * j;
-#pragma unroll
-                        for (int jj = 0; jj < NP; jj++) {
-                            const uint32_t w = rr[ZigZag<N>::idx[2 * jj]] | (rr[ZigZag<N>::idx[2 * jj + 1]] << 16);
-#pragma unroll
-                            for (int bb = 0; bb < NS; bb++) zp[bb][jj] = (b == bb) ? w : zp[bb][jj];
-                        }
-                    }
-                    j++;
-                }
-                wave_sync();
-            }
-        }
-    }
-    {  // statistics: FP64 requests of this wave (one store)
-        const uint32_t wsum = __builtin_amdgcn_readlane(wave_incl_scan_dpp(uint32_t(__popc(flags))), 63);
-        if (lane == 0) a.wave_fix[size_t(t) * (TPB / 64) + wv] = wsum;
-    }
-
-    WSTAMP(3);
-    asm volatile("; PHASE w3" ::: "memory");
-    // ------------------------------------------------------------ sizing + the wave's offsets
-    uint32_t blw[NS], rb[NS];
-    const uint32_t k0 = uint32_t(tif * TG + GW * wv) * 4u;  // the wave's first block (frame raster order)
-#pragma unroll
-    for (int b = 0; b < NS; b++) {
-        const bool valid = 64 * b + lane < nbw;
-        if (a.coef && valid) {
-            int16_t* dst = a.coef + (size_t(frame) * a.by * a.bx + k0 + 64 * b + lane) * NN;
-#pragma unroll
-            for (int k = 0; k < NN; k++) {
-                const int kz = ZigZagInv<N>::pos[k];
-                dst[k] = int16_t(kz & 1 ? (zp[b][kz >> 1] >> 16) : (zp[b][kz >> 1] & 0xFFFFu));
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        blw[b] = size_block<N>(zp[b], a.rle, &rb[b]);
-        rb[b] = valid ? rb[b] : 0u;
-        asm volatile("" : "+v"(blw[b]), "+v"(rb[b]));
-#pragma unroll
-        for (int j = 0; j < NP; j++) asm volatile("" : "+v"(zp[b][j]));
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    // slot pairs packed into 16-bit halves (a slot holds <= 64 * 252 bits)
-    const uint32_t s01 = rb[0] | (rb[1] << 16), s23 = rb[2] | (rb[3] << 16);
-    const uint32_t i01 = wave_incl_scan_dpp(s01), i23 = wave_incl_scan_dpp(s23);
-    const uint32_t t01 = __builtin_amdgcn_readlane(i01, 63), t23 = __builtin_amdgcn_readlane(i23, 63);
-    const uint32_t e01 = i01 - s01, e23 = i23 - s23;  // exclusive, per half (no borrow: each half >= 0)
-    uint32_t T[NS], off[NS];
-    T[0] = t01 & 0xFFFFu;
-    T[1] = t01 >> 16;
-    T[2] = t23 & 0xFFFFu;
-    T[3] = t23 >> 16;
-    off[0] = e01 & 0xFFFFu;
-    off[1] = e01 >> 16;
-    off[2] = e23 & 0xFFFFu;
-    off[3] = e23 >> 16;
-    const uint32_t S1 = T[0], S2 = S1 + T[1], S3 = S2 + T[2], Tw = S3 + T[3];
-    if (lane == 0) misc[wv] = Tw;
-    WSTAMP(4);
-    asm volatile("; PHASE w4" ::: "memory");
-    lds_barrier();  // ---- the tile's bit count and this wave's place in it
-    WSTAMP(5);
-    asm volatile("; PHASE w5" ::: "memory");
-
-    uint32_t A = 0, W = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        const uint32_t v = __builtin_amdgcn_readfirstlane(misc[w]);
-        A += v;
-        W += (w < wv) ? v : 0u;
-    }
-    if (tid == 0) chain_publish_count(a.st, t, chain_pos, a.tag, A);  // successors may resolve now
-    // look-back probes, in flight while emitting.  A launch too small to fill the chip (deep_lb:
-    // its tiles reach their look-back together, so a tile's nearest inclusive prefix is far away):
-    // the four waves read predecessors [64 DW wv, 64 DW (wv + 1)) in DW windows each -- 256 DW in
-    // one round trip; otherwise wave 0 reads the nearest kProbe0.
-    constexpr int DW = 2;
-    const bool deep = a.deep_lb != 0;
-    Probe pr[DW];
-#pragma unroll
-    for (int i = 0; i < DW; i++) pr[i] = Probe{0, 0, 0};
-    if (chain_pos != 0) {
-        if (deep) {
-#pragma unroll
-            for (int i = 0; i < DW; i++) pr[i] = probe_issue(a.st, t, chain_pos, step, 64 * (DW * wv + i), 64);
-        } else if (wv == 0) {
-            pr[0] = probe_issue(a.st, t, chain_pos, step, 0, kProbe0);
-        }
-    }
-
-    // slot-pair images: slots 0 and 1, then slots 2 and 3, each pair as ONE bit image from word 0
-    // of the wave's region (a pair holds <= 2 * 64 * 252 bits = 1008 words); emission takes
-    // absolute LDS bit addresses (scatter_bits' ds_or addresses LDS from byte 0)
-    const uint32_t reg_bit0 = uint32_t(wv * kWReg) * 32u;
-    const uint32_t Sb[NS] = {0u, S1, S2, S3};
-    auto zero_img = [&](uint32_t bits) {
-        const uint32_t nq = (bits + 127u) >> 7;  // 16-byte groups
-        for (uint32_t q = lane; q < nq; q += 64) *reinterpret_cast<u32x4*>(reg + 4 * q) = u32x4{0u, 0u, 0u, 0u};
-    };
-    auto emit_slot = [&](int b) {  // slot b at its place in its pair's image
-        if (rb[b]) {
-            const uint32_t p = reg_bit0 + (Sb[b] - Sb[b & 2]) + off[b];
-            if (a.tri && a.rle) emit_block3(smem, p, zp[b], blw[b]);
-            else emit_block2<N>(smem, p, zp[b], blw[b], a.rle);
-        }
-    };
-    zero_img(S2);
-    wave_sync();
-    emit_slot(0);
-    emit_slot(1);
-    wave_sync();
-    WSTAMP(6);
-    asm volatile("; PHASE w6" ::: "memory");
-    if (lane == 0 && Tw) misc[4 + wv] = reg[0];  // the wave's first 32 bits
-
-    // ------------------------------------------------------------ look-back (wave 0)
-    const bool chain_last = a.segmented ? (tif == a.tiles_per_frame - 1) : (t == a.ntiles - 1);
-    uint32_t* const out = a.out + (a.segmented ? uint64_t(frame) * a.out_pitch_words : 0ull);
-    if (deep && chain_pos != 0) {
-        // every wave sums its windows in order, up to the first with an inclusive prefix (read
-        // again until every value it needs is published; its predecessors never wait on this
-        // tile), for wave 0 to combine
-        uint64_t sm = 0;
-        bool found = false;
-        unsigned spins = 0;
-        for (;;) {
-            bool ready = true;
-            sm = 0;
-            found = false;
-#pragma unroll
-            for (int i = 0; i < DW; i++) {
-                const WinSum r = window_sum(pr[i], chain_pos, 64 * (DW * wv + i), 64, a.tag);
-                if (!found) {
-                    ready = ready && r.ready;
-                    sm += r.sum;
-                    found = r.found;
-                }
-            }
-            if (ready) break;
-            if (++spins > kSpinLimit) {
-                if (lane == 0) atomicAdd(&a.err[0], 1u);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-            for (int i = 0; i < DW; i++) pr[i] = probe_issue(a.st, t, chain_pos, step, 64 * (DW * wv + i), 64);
-        }
-        if (lane == 0) {
-            misc[18 + 2 * wv] = uint32_t(sm);
-            misc[19 + 2 * wv] = uint32_t(sm >> 32);
-            misc[26 + wv] = found ? 1u : 0u;
-        }
-        lds_barrier();
-    }
-    if (wv == 0) {
-        uint64_t excl = 0;
-        uint32_t ptail = 0, pend = 0;
-        if (chain_pos == 0) {
-            // chain start: the bits before start_bit belong to the caller (header)
-            const uint32_t s = uint32_t(start_bit & 31);
-            ptail = s ? (bswap32(out[start_bit >> 5]) >> (32 - s)) : 0u;
-        } else {
-            bool done = false;
-            if (deep) {  // the waves' sums in predecessor order, up to the first window with an inclusive prefix
-#pragma unroll
-                for (int w = 0; w < 4; w++) {
-                    if (!done) {
-                        excl += uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(misc[18 + 2 * w]))) |
-                                (uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(misc[19 + 2 * w]))) << 32);
-                        done = __builtin_amdgcn_readfirstlane(misc[26 + w]) != 0;
-                    }
-                }
-                if (!done) excl = 0;  // more than 256 DW predecessors back: the wave-0 walk from the start
-            }
-            if (!done) {
-                const Probe p0 = deep ? probe_issue(a.st, t, chain_pos, step, 0, kProbe0) : pr[0];
-                excl = lookback_wave<IE_W_AHEAD, IE_W_LBW>(p0, a.st, t, chain_pos, step, a.tag, a.err, nullptr, deep);
-            }
-            const bool have = uint32_t(pr[0].gt >> 56) == a.tag;  // (lane 0's probe read the tail)
-            const bool split = ((start_bit + excl) & 31) != 0;
-            ptail = have ? uint32_t(pr[0].gt) : 0u;
-            pend = (!have && split) ? 1u : 0u;
-        }
-        if (lane == 0) {
-            if (chain_pos != 0) publish(a.st, t, 1, a.tag, excl + A);
-            misc[8] = uint32_t(excl);
-            misc[9] = uint32_t(excl >> 32);
-            misc[10] = ptail;
-            misc[11] = pend;
-            const uint64_t P = start_bit + excl;
-            if (tif == 0) a.frame_start[frame] = P;
-            if (chain_last) a.chain_end[a.segmented ? frame : 0] = P + A;
-        }
-    }
-    WSTAMP(7);
-    asm volatile("; PHASE w7" ::: "memory");
-    lds_barrier();  // ---- the tile's position
-    WSTAMP(8);
-    asm volatile("; PHASE w8" ::: "memory");
-
-    // ------------------------------------------------------------ store, slot by slot
-    if (Tw) {
-        // (readfirstlane returns int: zero-extend each half, or a prefix of 2^31 bits or more
-        // would sign-extend into the high word)
-        const uint64_t excl = uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(misc[8]))) |
-                              (uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(misc[9]))) << 32);
-        const uint64_t Xw = start_bit + excl + W;
-        const bool pend = __builtin_amdgcn_readfirstlane(misc[11]) != 0u;
-        // the wave's first word is written by the previous wave (or, pending, later by this one)
-        const uint64_t skipw = ((Xw & 31) && (wv > 0 || pend)) ? (Xw >> 5) : ~0ull;
-        uint32_t prev = (wv == 0) ? __builtin_amdgcn_readfirstlane(misc[10]) : 0u;
-        // HIST: bytes at or past the chain's last byte are padding
-        const HistCountT<HR> hc{hl, chain_last ? (start_bit + excl + A + 7) / 8 : ~0ull, uint32_t(lane % HR)};
-        auto count = [&](uint64_t gw, uint32_t v) {
-            if constexpr (HIST) hc(gw, v);
-        };
-        // pair 0 is stored as soon as the tile's position is known; the region then takes pair 1
-        // (one wave's LDS operations complete in order)
-        auto store_pair = [&](uint32_t S0, uint32_t n) {
-            if (!n) return;
-            const uint64_t Xb = Xw + S0;
-            const uint32_t nw = uint32_t(((Xb + n) >> 5) - (Xb >> 5));
-            if constexpr (HIST) store_slot(out, reg, Xb, nw, ((Xb >> 5) == skipw) ? 1u : 0u, prev, lane, hc);
-            else store_slot(out, reg, Xb, nw, ((Xb >> 5) == skipw) ? 1u : 0u, prev, lane);
-            prev = slot_tail32(reg, n, prev);
-        };
-        if constexpr (HIST) {
-            if (wv == 0 && chain_pos == 0)  // the words before the first record word: the caller's header
-                for (uint32_t i = lane; i < uint32_t(start_bit >> 5); i += 64) hc(i, out[i]);
-        }
-        store_pair(0u, S2);
-        WSTAMP(9);
-    asm volatile("; PHASE w9" ::: "memory");
-        if (Tw > S2) {
-            wave_sync();  // pair 0's image has been read
-            zero_img(Tw - S2);
-            wave_sync();
-            emit_slot(2);
-            emit_slot(3);
-            wave_sync();
-            store_pair(S2, Tw - S2);
-        }
-        const uint64_t E = Xw + Tw;
-        const uint32_t e = uint32_t(E) & 31u;
-        if (lane == 0) {
-            if (e && (wv < wlast || chain_last)) {  // the wave's last, partial word
-                const uint32_t v = bswap32((prev << (32u - e)) | (wv < wlast ? misc[4 + wv + 1] >> e : 0u));
-                out[E >> 5] = v;
-                count(E >> 5, v);
-            }
-            if (wv == wlast) publish(a.st, t, 2, a.tag, prev);  // the tile's last 32 bits
-            if (wv == 0 && pend) {  // the first word, with the predecessor's tail
-                const uint32_t pt = wait_tail(a.st, t - step, a.tag, a.err);
-                const uint32_t s = uint32_t(Xw) & 31u;
-                const uint32_t v = bswap32((pt << (32u - s)) | (misc[4] >> s));
-                out[Xw >> 5] = v;
-                count(Xw >> 5, v);
-            }
-        }
-        WSTAMP(10);
-        WRTSTAMP(15);
-    asm volatile("; PHASE w10" ::: "memory");
-    }
-    if constexpr (HIST) {
-        lds_barrier();  // every wave's bytes counted
-        uint32_t c = 0;
-#pragma unroll
-        for (int r = 0; r < HR; r++) c += hl[tid * HR + r];
-        if (c) atomicAdd(&a.hist[size_t(frame) * 256 + tid], c);
-    }
-}
-
 // =============================================================================================
-// encode4p_kernel -- encode4w_kernel's tile (wave-local slots, the same emission, look-back and
-// store) with the integer half of the transform on the matrix pipe.  One workgroup per tile, the
-// tiles in dispatch order (ticket mode, the host's fallback after a look-back timeout, runs
-// encode4w_kernel).
+// encode4p_kernel<HIST, TICKET> -- the 4x4 FAST encoder with WAVE-LOCAL emission and the integer
+// half of the transform on the matrix pipe.
+//
+// Same tile (1024 blocks, 256 threads, one chain element, the same chain granules) and the same
+// FP64 fix-up as encode_kernel<4, false> (the Trk exactness argument carries over with quot4j's own
+// limits), laid out so that a wave rarely needs its workgroup:
+//   * wave w owns the tile's blocks [256w, 256w + 256) (64 groups of four, raster order); lane l
+//     computes block 64b + l of that run in SLOT b = 0..3, so a slot is 64 consecutive blocks of
+//     the stream and one wave scan (DPP) places every record inside its slot;
+//   * the pixels land in the wave's own LDS region by DMA as [row][256 blocks] words (a slot
+//     reads them conflict-free, no other wave touches them); after the fix-up the same region
+//     holds the wave's slot images (all four at once when they fit, slot pairs in turn otherwise);
+//   * a word shared by two waves of the tile is written by the earlier wave, which ORs in the
+//     later wave's first bits (its head word, saved in LDS before the position barrier); a word
+//     shared with the predecessor tile is completed with that tile's tail granule as in
+//     encode_kernel.
+// Preconditions (launch_encode checks them): whole 16-byte groups (vec_ok, bx % 4 == 0), at
+// least 8 groups in every tile (groups_per_frame % 8 == 0: every wave segment >= 160 bits) and
+// slot images that fit half a region (rec_bits <= 252).
+// HIST (ie_encode_images_counted): every stored byte also counted into a per-tile LDS histogram
+// (kWHistRep copies of 256 words), merged into a.hist[frame] at the end -- the Huffman pass's byte
+// counts without reading the stream back.
+// One workgroup per tile.  TICKET = false: tile = blockIdx.x, the tiles in dispatch order.
+// TICKET = true (the host's redo after a look-back timeout, IE_FORCE_TICKET): tile = an atomic
+// ticket, so tile order is start order whatever the dispatcher does.  Every wait in the kernel is
+// either on the waves of the tile's own workgroup (the count flags, the barriers) or on chain
+// predecessors t - step (d + 1) -- the first probe and lookback_wave's windows, the deep windows
+// of all four waves, wait_tail(t - step) --, which hold lower tickets and have therefore started
+// and wait only on still lower ones: ticket order cannot deadlock.
 //   * Matrix pipe: per slot (64 blocks of one wave), ONE v_mfma_i32_32x32x32_i8 forms the sixteen
 //     integer basis sums J of every block (ie_dct.h quot4j: pixels as signed bytes x ^ 0x80, the
 //     {-1,0,1} A fragment from EncTables::mfma_w), which replaces the 16 pixel unpacks and the
 //     integer butterflies on the VALU; the FP32 stage (36 mul/fma) and the rounding follow, with
-//     the tie limits of quot4j's own tracked run (lim4j).  The FP64 fix-up, sizing, emission and
-//     store are encode4w_kernel's.
+//     the tie limits of quot4j's own tracked run (lim4j).
 //   * Count by polling: each wave stores its bit count and a flag; wave 0 alone waits for the
 //     four flags, publishes the tile aggregate and issues its look-back probe, while waves 1-3 go
 //     straight on to their emission.  One workgroup barrier per tile (the position).
@@ -1915,10 +1419,11 @@ __global__ __launch_bounds__(256, IE_W_WAVES) void encode4w_kernel(EncArgs a, co
 // =============================================================================================
 constexpr int kPWfrag = 256;  // the matrix-pipe A fragments [64 lanes][4 words]
 // encode4p_kernel's misc words: [0, 4) wave bit counts, H the waves' head words, E the tile's
-// exclusive prefix (2), PT the tail before the chain start, PD the pending first word, F the
-// count flags, D the deep look-back sums (2 per wave), FD their found flags
+// exclusive prefix (2), PT the tail before the chain start, PD the pending first word, TK the
+// tile's ticket (TICKET), F the count flags, D the deep look-back sums (2 per wave), FD their
+// found flags
 struct PMisc {
-    static constexpr int H = 4, E = 8, PT = 10, PD = 11, F = 16, D = 20, FD = 28, S = 32;
+    static constexpr int H = 4, E = 8, PT = 10, PD = 11, TK = 12, F = 16, D = 20, FD = 28, S = 32;
     static_assert(FD + 4 <= S && F % 4 == 0, "misc layout");
 };
 constexpr int p_lds_bytes() { return (4 * 4 * 256 + 4 * kWTask + PMisc::S + kPWfrag) * 4 + kWRows * 8; }
@@ -1926,7 +1431,9 @@ constexpr int p_lds_bytes() { return (4 * 4 * 256 + 4 * kWTask + PMisc::S + kPWf
 typedef int v4i32 __attribute__((ext_vector_type(4)));
 typedef int v16i32 __attribute__((ext_vector_type(16)));
 
-// round_block_lean4 with the limits passed in (quot4j's own)
+// round_block<4> with the limits passed in (quot4j's own), the rounding done pair by pair in
+// zig-zag order and each packed word pinned as soon as it exists: the 16 magic-added quotients
+// never live at once (register pressure of the fourth slot).  Same results bit for bit.
 __device__ __forceinline__ float round_block_lean4j(const float (&t)[16], uint32_t (&zp)[8], uint32_t* sflags, bool dcx,
                                                     float l0, float l1, float l2) {
     constexpr int S0 = Structural<4>::k[0], S1 = Structural<4>::k[1], S2 = Structural<4>::k[2];
@@ -1976,7 +1483,7 @@ __device__ __forceinline__ float round_block_lean4j(const float (&t)[16], uint32
 #define IE_P_ABL 0  // (profiling builds) phases left out: 1 FP64 fix-up, 2 emission, 4 look-back, 8 store, 16 transform
 #endif
 
-template <bool HIST>
+template <bool HIST, bool TICKET>
 __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void encode4p_kernel(EncArgs a_, const EncTables* __restrict__ tab) {
     constexpr int N = 4, NN = 16, NP = 8, NS = 4, PS = 2;  // slots per lane, slots per pair
     constexpr int GW = 64, BW = 256, TG = 256;  // groups / blocks per wave, groups per tile
@@ -1992,13 +1499,18 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
     uint32_t* const hl = wl + kPWfrag;  // HIST: the tile's byte histogram
     constexpr int HR = kWHistRep, HWORDS = 256 * HR;
     double* const srow = reinterpret_cast<double*>(hl + (HIST ? HWORDS : 0));
-    const int t = int(blockIdx.x);
+    int t = int(blockIdx.x);
+    if constexpr (TICKET) {  // tiles in ticket order; t wave-uniform, in a scalar register
+        if (threadIdx.x == 0) misc[ML::TK] = uint32_t(atomicAdd(a_.ticket, 1ull) - a_.ticket_base);
+        lds_barrier();
+        t = __builtin_amdgcn_readfirstlane(int(misc[ML::TK]));
+    }
     // The launch arguments are read through a pointer to the kernel-argument segment (constant
     // address space): the geometry words in one scalar round trip (load_geo), the rest where used.
     using KArgs = const __attribute__((address_space(4))) EncArgs;
     KArgs* ka = (KArgs*)(__builtin_amdgcn_kernarg_segment_ptr());
     const GeoArgs ga = load_geo(ka);
-    if (t >= ga.ntiles) return;
+    if (t >= ga.ntiles) return;  // (a ticket desync after a failed launch: never touch memory)
     // The lane id is re-derived at every phase (fresh_lane): a lane-derived VGPR held across the
     // whole tile was spilled at higher occupancy.
     int lane = fresh_lane();
@@ -2087,7 +1599,7 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
     WSTAMP(2);
     asm volatile("; PHASE p2" ::: "memory");
 
-    // ------------------------------------------------------------ FP64 fix-up (encode4w_kernel's)
+    // ------------------------------------------------------------ FP64 fix-up
     lane = fresh_lane();
     auto block_px = [&](int b, int owner) {
         BlockPx<N> px;
@@ -2122,6 +1634,9 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
                 res[lane] = uint32_t(y) & 0xFFFFu;
             }
             wave_sync();
+            // the owners take their results back: the flagged positions in bit order, each a
+            // constant register (the three structural coefficients are high halves of packed
+            // words), so no per-request select over every slot and coefficient
             i = pre - r0;
 #pragma unroll
             for (int b = 0; b < NS; b++)
@@ -2129,12 +1644,15 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
                 for (int ss = 0; ss < 3; ss++) {
                     if ((sf >> (4 * b + ss)) & 1u) {
                         const int zw = Structural<N>::zpos(ss) >> 1;
+                        static_assert(Structural<4>::zpos(0) & Structural<4>::zpos(1) & Structural<4>::zpos(2) & 1,
+                                      "4x4 structural coefficients sit in high halves");
                         if (i < 64u) zp[b][zw] = __builtin_amdgcn_perm(res[i], zp[b][zw], 0x05040100u);  // res low -> high half
                         i++;
                     }
                 }
             wave_sync();
         }
+        // whole-block requests (rare): all 16 coefficients in FP64, one per lane, four blocks a round
         const uint32_t wf = flags & 0x8888u;
         if (__ballot(wf != 0)) {
             const uint32_t nb = __popc(wf);
@@ -2257,7 +1775,11 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
     uint32_t A = 0;  // (wave 0, or every wave in deep mode; the others after the position barrier)
 #pragma unroll
     for (int w = 0; w < 4; w++) A += __builtin_amdgcn_readfirstlane(misc[w]);
-    if (wv == 0 && lane == 0) chain_publish_count(a.st, t, chain_pos, a.tag, A);
+    if (wv == 0 && lane == 0) chain_publish_count(a.st, t, chain_pos, a.tag, A);  // successors may resolve now
+    // look-back probes, in flight while emitting.  Deep (a launch too small to fill the chip: its
+    // tiles reach their look-back together, so a tile's nearest inclusive prefix is far away): the
+    // four waves read predecessors [64 DW wv, 64 DW (wv + 1)) in DW windows each -- 256 DW in one
+    // round trip; otherwise wave 0 reads the nearest kProbe0.
     constexpr int DW = 2;
     Probe pr[DW];
 #pragma unroll
@@ -2308,6 +1830,9 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
     const bool chain_last = a.segmented ? (tif == a.tiles_per_frame - 1) : (t == a.ntiles - 1);
     uint32_t* const out = a.out + (a.segmented ? uint64_t(frame) * a.out_pitch_words : 0ull);
     if (deep && chain_pos != 0) {
+        // every wave sums its windows in order, up to the first with an inclusive prefix (read
+        // again until every value it needs is published; its predecessors never wait on this
+        // tile), for wave 0 to combine
         uint64_t sm = 0;
         bool found = false;
         unsigned spins = 0;
@@ -2357,7 +1882,7 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
                         done = __builtin_amdgcn_readfirstlane(misc[ML::FD + w]) != 0;
                     }
                 }
-                if (!done) excl = 0;
+                if (!done) excl = 0;  // more than 256 DW predecessors back: the wave-0 walk from the start
             }
             if (!done) {
                 const Probe p0 = deep ? probe_issue(a.st, t, chain_pos, step, 0, kProbe0) : pr[0];
@@ -2397,12 +1922,16 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
 
     // ------------------------------------------------------------ store, slot pair by slot pair
     if (Tw) {
+        // (readfirstlane returns int: zero-extend each half, or a prefix of 2^31 bits or more
+        // would sign-extend into the high word)
         const uint64_t excl = uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(misc[ML::E]))) |
                               (uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(misc[ML::E + 1]))) << 32);
         const uint64_t Xw = start_bit + excl + W;
         const bool pend = __builtin_amdgcn_readfirstlane(misc[ML::PD]) != 0u;
+        // the wave's first word is written by the previous wave (or, pending, later by this one)
         const uint64_t skipw = ((Xw & 31) && (wv > 0 || pend)) ? (Xw >> 5) : ~0ull;
         uint32_t prev = (wv == 0) ? __builtin_amdgcn_readfirstlane(misc[ML::PT]) : 0u;
+        // HIST: bytes at or past the chain's last byte are padding
         const HistCountT<HR> hc{hl, chain_last ? (start_bit + excl + A + 7) / 8 : ~0ull, uint32_t(lane % HR)};
         auto count = [&](uint64_t gw, uint32_t v) {
             if constexpr (HIST) hc(gw, v);
@@ -2416,7 +1945,7 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
             prev = slot_tail32(reg, n, prev);
         };
         if constexpr (HIST) {
-            if (wv == 0 && chain_pos == 0)
+            if (wv == 0 && chain_pos == 0)  // the words before the first record word: the caller's header
                 for (uint32_t i = lane; i < uint32_t(start_bit >> 5); i += 64) hc(i, out[i]);
         }
         const uint64_t E = Xw + Tw;
@@ -2464,16 +1993,13 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
 }
 
 // Returns the FP64-statistics words per tile the launched kernel writes (its waves per tile).
-int launch_encode4w(const EncArgs& a, hipStream_t s) {
-    if (!a.ticket) {  // dispatch order: encode4p_kernel, one workgroup per tile
-        const size_t lds = p_lds_bytes() + (a.hist ? 1024 * kWHistRep : 0);
-        if (a.hist) hipLaunchKernelGGL(encode4p_kernel<true>, dim3(a.ntiles), dim3(256), lds, s, a, a.tab);
-        else hipLaunchKernelGGL(encode4p_kernel<false>, dim3(a.ntiles), dim3(256), lds, s, a, a.tab);
-        return 4;
-    }
-    // ticket mode (the host's redo after a look-back timeout): tiles in ticket order
-    if (a.hist) hipLaunchKernelGGL(encode4w_kernel<true>, dim3(a.ntiles), dim3(256), kWLdsBytes + 1024 * kWHistRep, s, a, a.tab);
-    else hipLaunchKernelGGL(encode4w_kernel<false>, dim3(a.ntiles), dim3(256), kWLdsBytes, s, a, a.tab);
+// One workgroup per tile, in dispatch order or (a.ticket: the host's redo after a look-back
+// timeout) in ticket order.
+int launch_encode4p(const EncArgs& a, hipStream_t s) {
+    const size_t lds = p_lds_bytes() + (a.hist ? 1024 * kWHistRep : 0);
+    auto kernel = a.hist ? (a.ticket ? encode4p_kernel<true, true> : encode4p_kernel<true, false>)
+                         : (a.ticket ? encode4p_kernel<false, true> : encode4p_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(a.ntiles), dim3(256), lds, s, a, a.tab);
     return 4;
 }
 
@@ -2502,14 +2028,12 @@ int encode_small_tiles() {
 
 int encode_threads_per_tile() { return kEncTPB; }
 
-int launch_encode4w(const EncArgs& a, hipStream_t s);
-
 int launch_encode(const EncArgs& a0, int n, bool exact, hipStream_t s, int bpt) {
     EncArgs a = a0;
-    // 4x4 FAST over whole 16-byte groups: the wave-local encoders (encode4p_kernel)
+    // 4x4 FAST over whole 16-byte groups: the wave-local encoder (encode4p_kernel)
     if (n == 4 && !exact && bpt == 4 && a.vec_ok && a.bx % 4 == 0 &&
         a.groups_per_frame % 8 == 0 && a.rec_bits <= 252 && !a.ablate)
-        return launch_encode4w(a, s);
+        return launch_encode4p(a, s);
     a.img_words = image_words_for(n, bpt, a.rec_bits);
     if (n == 4 && a.img_words < fix_words<4>()) a.img_words = fix_words<4>();
     if (n == 8 && a.img_words < kFix8Words) a.img_words = kFix8Words;

@@ -284,3 +284,116 @@ def test_small_launch_lookback_matches_batch_path(w, h, f, tmp_path):
         assert r.returncode == 0, r.stderr[-2000:]
         outs.append(r.stdout.strip().splitlines()[-1])
     assert outs[0] == outs[1]
+
+
+# ---- ticket mode (the host's redo after a look-back timeout; IE_FORCE_TICKET takes it from the
+# first launch).  Python cannot observe which kernel ran: the "wave-local" shapes below are chosen
+# to satisfy launch_encode's preconditions for encode4p_kernel (4x4 FAST, w % 16 == 0,
+# groups_per_frame = (w / 16) * (h / 4) a multiple of 8, 16-byte aligned rows, and matrix.txt's
+# rec_bits <= 252), so they run encode4p_kernel<HIST, true>; 200x56 fails w % 16 and runs
+# encode_kernel's ticket path.
+
+def _ticket_codec(monkeypatch, ticket=True, fake_timeouts=None):
+    """A codec of its own: ie_create reads the debug switches."""
+    from imageencoder_amd import Codec
+    if ticket:
+        monkeypatch.setenv("IE_FORCE_TICKET", "1")
+    else:
+        monkeypatch.delenv("IE_FORCE_TICKET", raising=False)
+    if fake_timeouts is not None:
+        monkeypatch.setenv("IE_FAKE_TIMEOUTS", str(fake_timeouts))
+    return Codec(0, O.read_matrix("matrix.txt", 4), 4)
+
+
+def _check_vs_oracle(codec, oracle, y, w, h, f, start_bit, rle):
+    from imageencoder_amd import stream_bound
+    q = O.read_matrix("matrix.txt", 4)
+    out = np.zeros(stream_bound(w, h, 4, f, start_bit), dtype=np.uint8)
+    fb, end = codec.encode_frames(y, w, h, out, start_bit=start_bit, nframes=f, rle=rle)
+    exp, eend, efb = oracle.encode_blocks(y, 4, q, rle, start_bit)
+    assert end == eend and np.array_equal(fb, efb)
+    nb = (end + 7) // 8
+    assert out[:nb].tobytes() == exp[:nb].tobytes()
+
+
+@pytest.mark.parametrize("w,h,f", [
+    (16, 32, 1),      # wave-local: one tile of 8 groups, one wave
+    (256, 64, 3),     # wave-local: exactly one full tile per frame, a three-tile chain
+    (1024, 136, 2),   # wave-local: nine tiles per frame, the last with only waves 0-1 populated
+    (200, 56, 3),     # w % 16 != 0: the general kernel's ticket path
+])
+def test_ticket_mode_vs_oracle(oracle, monkeypatch, w, h, f):
+    """Tiles ordered by the atomic ticket: encode_frames against the oracle bit for bit (end bit,
+    per-frame bits, bytes), start bits 0 and 165, RLE on and off."""
+    codec = _ticket_codec(monkeypatch)
+    try:
+        for start_bit, rle, kind in ((0, True, "M"), (0, False, "U"), (165, True, "U"), (165, False, "M")):
+            y = synth.frames(kind, w, h, f, seed=31 + start_bit)
+            _check_vs_oracle(codec, oracle, y, w, h, f, start_bit, rle)
+    finally:
+        codec.close()
+
+
+def test_ticket_mode_fills_the_chip(monkeypatch):
+    """Nine 1080p frames, 1 143 tiles (wave-local; no deep look-back, each frame's last tile 144
+    groups), device in and out: FAST in ticket mode == EXACT byte for byte, equal frame bits."""
+    import torch
+    from imageencoder_amd import stream_bound
+    codec = _ticket_codec(monkeypatch)
+    try:
+        w, h, f = 1920, 1080, 9
+        y = torch.from_numpy(synth.frames("M", w, h, f, seed=4243)).cuda()
+        a = torch.zeros(stream_bound(w, h, 4, f), dtype=torch.uint8, device="cuda")
+        b = torch.zeros_like(a)
+        fa, ea = codec.encode_frames(y, w, h, a, nframes=f, mode=MODE_FAST)
+        fb, eb = codec.encode_frames(y, w, h, b, nframes=f, mode=MODE_EXACT)
+        assert ea == eb and np.array_equal(fa, fb)
+        assert torch.equal(a[: (ea + 7) // 8], b[: (eb + 7) // 8])
+    finally:
+        codec.close()
+
+
+@pytest.mark.parametrize("w,h,f,start_bit", [(256, 128, 4, 165), (1024, 136, 2, 0)])
+def test_ticket_mode_counted_histogram(monkeypatch, w, h, f, start_bit):
+    """The counted, segmented encode in ticket mode (wave-local shapes): the fused byte counts
+    equal the separate histogram pass's and a host bincount of each image's bytes; the first
+    positions match too."""
+    import torch
+    from imageencoder_amd import stream_bound
+    codec = _ticket_codec(monkeypatch)
+    try:
+        pitch = (stream_bound(w, h, 4, 1, start_bit) + 255) // 256 * 256
+        y = torch.from_numpy(synth.frames("M", w, h, f, seed=77)).cuda()
+        rng = np.random.default_rng(5)
+        out = torch.zeros(pitch * f, dtype=torch.uint8)
+        nh = (start_bit + 7) // 8
+        for k in range(f):  # header bytes (random), bits from start_bit on left zero
+            hdr = rng.integers(0, 256, nh, dtype=np.uint8)
+            if start_bit % 8:
+                hdr[-1] &= np.uint8((0xFF00 >> (start_bit % 8)) & 0xFF)
+            out[k * pitch: k * pitch + nh] = torch.from_numpy(hdr)
+        out = out.cuda()
+        codec.encode_images(y, w, h, out, out_pitch=pitch, nframes=f, start_bit=start_bit, count_bytes=True)
+        h_fused, f_fused = codec.huffman_hist_after_encode(out, pitch, f)
+        ends = codec.encode_images(y, w, h, out, out_pitch=pitch, nframes=f, start_bit=start_bit)
+        h_pass, f_pass = codec.huffman_hist_after_encode(out, pitch, f)
+        host = out.cpu().numpy()
+        for k in range(f):
+            nb = (int(ends[k]) + 7) // 8
+            want = np.bincount(host[k * pitch: k * pitch + nb], minlength=256).astype(np.uint32)
+            np.testing.assert_array_equal(h_pass[k], want)
+            np.testing.assert_array_equal(h_fused[k], want)
+        np.testing.assert_array_equal(f_fused, f_pass)
+    finally:
+        codec.close()
+
+
+def test_timeout_redo_in_ticket_mode_vs_oracle(oracle, monkeypatch):
+    """The real redo: one reported look-back timeout (IE_FAKE_TIMEOUTS=1, no IE_FORCE_TICKET) makes
+    the host run the launch again in ticket mode; host output, start bit 165, against the oracle."""
+    codec = _ticket_codec(monkeypatch, ticket=False, fake_timeouts=1)
+    try:
+        w, h, f = 256, 64, 3
+        _check_vs_oracle(codec, oracle, synth.frames("M", w, h, f, seed=58), w, h, f, 165, True)
+    finally:
+        codec.close()

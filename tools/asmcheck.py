@@ -125,10 +125,10 @@ def static_lds(path):
 BUDGETS = {
     "_ZN2ie13encode_kernelILi4ELb0ELb0ELi4EEEvNS_7EncArgsEPKNS_9EncTablesE": (5, 0),
     "_ZN2ie13encode_kernelILi8ELb0ELb0ELi1EEEvNS_7EncArgsEPKNS_9EncTablesE": (4, 0),
-    "_ZN2ie15encode4w_kernelILb0EEEvNS_7EncArgsEPKNS_9EncTablesE": (6, 0),
-    "_ZN2ie15encode4w_kernelILb1EEEvNS_7EncArgsEPKNS_9EncTablesE": (6, 0),
-    "_ZN2ie15encode4p_kernelILb0EEEvNS_7EncArgsEPKNS_9EncTablesE": (6, 0),
-    "_ZN2ie15encode4p_kernelILb1EEEvNS_7EncArgsEPKNS_9EncTablesE": (6, 0),
+    "_ZN2ie15encode4p_kernelILb0ELb0EEEvNS_7EncArgsEPKNS_9EncTablesE": (6, 0),
+    "_ZN2ie15encode4p_kernelILb1ELb0EEEvNS_7EncArgsEPKNS_9EncTablesE": (6, 0),
+    "_ZN2ie15encode4p_kernelILb0ELb1EEEvNS_7EncArgsEPKNS_9EncTablesE": (6, 0),
+    "_ZN2ie15encode4p_kernelILb1ELb1EEEvNS_7EncArgsEPKNS_9EncTablesE": (6, 0),
 }
 def main(paths):
     rc = 0
@@ -143,7 +143,7 @@ def main(paths):
         # the encoder's bit image is addressed from LDS byte 0 (scatter_bits' inline ds_or): its
         # kernels must allocate no static LDS, so the dynamic area starts there
         for name, size in static_lds(p).items():
-            if ("encode_kernel" in name or "encode4w_kernel" in name or "encode4p_kernel" in name) and size != 0:
+            if ("encode_kernel" in name or "encode4p_kernel" in name) and size != 0:
                 rc = 1
                 print(f"{p}: {name} allocates {size} B of static LDS (scatter_bits assumes 0)", file=sys.stderr)
         bad, kernels = scan(p)

@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/fetchab; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-WL=${WL:-c4}; K="encode4p_kernel<false>"; G=""; [ $WL = c4 ] && G=2080768
+WL=${WL:-c4}; K="encode4p_kernel<false, false>"; G=""; [ $WL = c4 ] && G=2080768
 BOPT="--full --steps 6 --warmup 1 --no-cpu --no-single-frame --no-e2e --no-decode --no-gop --no-check"
 for v in ${LIBS:-product}; do
   L=$R/imageencoder_amd/lib/libie_hip.so; [ $v = product ] || L=$R/imageencoder_amd/lib/var_$v/libie_hip.so

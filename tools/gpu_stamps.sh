@@ -1,4 +1,4 @@
-# encode4w/4p per-wave phase stamps (IE_PROFILE builds) of one NF-frame 4K launch, NF in $NFS, for
+# encode4p per-wave phase stamps (IE_PROFILE builds) of one NF-frame 4K launch, NF in $NFS, for
 # every variant library named in $VARS (imageencoder_amd/lib/var_NAME; default: prof)
 R=${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p $R/gpurun_out

@@ -1,4 +1,4 @@
-"""Summarise encode4w_kernel's per-wave phase stamps (IE_PROFILE build, IE_STAMPS=file: s_memtime at
+"""Summarise encode4p_kernel's per-wave phase stamps (IE_PROFILE build, IE_STAMPS=file: s_memtime at
 each phase boundary by every wave's lane 0, [tile][4 waves][12]) of one launch.
 usage: python tools/stamps_w.py stamps.bin [clock_ghz]"""
 import sys
