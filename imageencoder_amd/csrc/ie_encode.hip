@@ -587,6 +587,35 @@ __device__ __forceinline__ void emit_block3(uint32_t* img, uint32_t p, const uin
     }
 }
 
+// emit_block3's records when every bl of the wave's slot is <= 8: the header, Lw, z0 and z1 in one
+// field of 4 + 3*bl <= 28 bits, then the coefficients FOUR at a time (two packed words, 4*bl <= 32
+// bits) and z14, z15: 5 fields per block instead of 6.  Each field is built left-aligned, as
+// scatter_bits shifts it: a packed word gives (z_lo << bl) | z_hi in its low 2*bl bits by one
+// extract and one shift-or -- whatever lies above falls off the top of v_alignbit's funnel, so no
+// coefficient is masked on its own and no field is shifted left again.  The fields cover the same
+// 4 + 17*bl bits as emit_block3's, so the image needs no more slack.
+__device__ __forceinline__ void emit_block4(uint32_t p, const uint32_t (&zp)[8], uint32_t blw) {
+    const uint32_t bl = blw & 0xFFu, lw = blw >> 8, bl2 = 2u * bl;
+    const uint32_t up = 0u - bl2;  // (a shift count: the hardware takes its low 5 bits, 32 - 2*bl)
+    auto pr = [&](int j) -> uint32_t {  // word j's pair in the low 2*bl bits, garbage above
+        return (zp[j] << bl) | __builtin_amdgcn_ubfe(zp[j], 16u, bl);
+    };
+    auto put = [&](uint32_t u) {  // the left-aligned field u into the word pair at bit p
+        const uint32_t a = (p >> 3) & ~3u;
+        const uint32_t hi = u >> (p & 31u);
+        const uint32_t lo = __builtin_amdgcn_alignbit(u, 0u, p);
+        asm volatile("ds_or_b32 %0, %1\n\tds_or_b32 %0, %2 offset:4" ::"v"(a), "v"(hi), "v"(lo) : "memory");
+    };
+    put(__builtin_amdgcn_alignbit((bl << bl) | lw, pr(0) << (up & 31u), 4u + bl));
+    p += 4u + bl + bl2;
+#pragma unroll
+    for (int j = 1; j < 7; j += 2) {
+        put(__builtin_amdgcn_alignbit(pr(j), pr(j + 1) << (up & 31u), bl2));
+        p += 2u * bl2;
+    }
+    put(pr(7) << (up & 31u));
+}
+
 // Where tile t sits: its chain (frame / whole batch), its position in it and this thread's
 // group of blocks.
 struct TileGeo {
@@ -1607,6 +1636,7 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
         for (int r = 0; r < N; r++) px.w[r] = reg[r * BW + 64 * b + owner];
         return px;
     };
+    uint32_t wave_req = 0;  // statistics: FP64 requests of this wave
     if (!(IE_P_ABL & 1) && __ballot(flags != 0)) {
         const uint32_t sf = flags & 0x7777u;
         const uint32_t cnt = __popc(sf);
@@ -1614,43 +1644,92 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
         const uint32_t incl = wave_incl_scan_dpp(cnt);
         const uint32_t pre = incl - cnt;
         const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
-        for (uint32_t r0 = 0; r0 < total; r0 += 64) {
-            uint32_t m = sf, i = pre - r0;
-            while (m) {
-                const int bit = __ffs(m) - 1;
-                m &= m - 1;
-                if (i < 64u) task[i] = (uint32_t(lane) << 4) | uint32_t(bit);
-                i++;
+        wave_req = total;
+        auto task_y = [&](uint32_t tk) -> uint32_t {  // one structural coefficient in FP64
+            const int s = int(tk & 3u), b = int((tk >> 2) & 3u), owner = int(tk >> 4);
+            const BlockPx<N> px = block_px(b, owner);
+            const int k = Structural<N>::k[0] * (s == 0) + Structural<N>::k[1] * (s == 1) + Structural<N>::k[2] * (s == 2);
+            const int y = (IE_P_ABL & 32) ? int(px.w[0] & 1u)  // (profiling) no FP64 arithmetic (a small value: records stay in bound)
+                                          : exact_coef_row<N>(srow + k * NN, srow[NN * NN + k], srow[NN * NN + NN + k],
+                                                              srow[NN * NN + 2 * NN + k], px);
+            return uint32_t(y) & 0xFFFFu;
+        };
+        static_assert(Structural<4>::zpos(0) & Structural<4>::zpos(1) & Structural<4>::zpos(2) & 1,
+                      "4x4 structural coefficients sit in high halves");
+        constexpr int z0 = Structural<N>::zpos(0) >> 1, z1 = Structural<N>::zpos(1) >> 1, z2 = Structural<N>::zpos(2) >> 1;
+        static_assert(z0 != z1 && z1 != z2 && z0 != z2, "one structural coefficient per packed word");
+        if (total <= 64u) {
+            // One round (all but the densest waves), straight-line: every request has a task slot,
+            // so nothing is range-checked, and the owners read their results back slot by slot --
+            // a lane's requests of one slot are consecutive in res, so three unconditional reads
+            // per slot, six in flight at once, replace one dependent LDS round trip per flagged
+            // position.  (A read past a lane's last request, at most res[65], stays inside the
+            // task area or the words behind it and is not selected.)
+            if (sf) {
+                uint32_t m = sf, i = pre;
+                do {
+                    task[i++] = (uint32_t(lane) << 4) | uint32_t(__ffs(m) - 1);
+                    m &= m - 1;
+                } while (m);
             }
             wave_sync();
-            if (uint32_t(lane) < total - r0) {
-                const uint32_t tk = task[lane];
-                const int s = int(tk & 3u), b = int((tk >> 2) & 3u), owner = int(tk >> 4);
-                const BlockPx<N> px = block_px(b, owner);
-                const int k = Structural<N>::k[0] * (s == 0) + Structural<N>::k[1] * (s == 1) + Structural<N>::k[2] * (s == 2);
-                const int y = (IE_P_ABL & 32) ? int(px.w[0] & 1u)  // (profiling) no FP64 arithmetic (a small value: records stay in bound)
-                                              : exact_coef_row<N>(srow + k * NN, srow[NN * NN + k], srow[NN * NN + NN + k],
-                                                                  srow[NN * NN + 2 * NN + k], px);
-                res[lane] = uint32_t(y) & 0xFFFFu;
-            }
+            if (uint32_t(lane) < total) res[lane] = task_y(task[lane]);
             wave_sync();
-            // the owners take their results back: the flagged positions in bit order, each a
-            // constant register (the three structural coefficients are high halves of packed
-            // words), so no per-request select over every slot and coefficient
-            i = pre - r0;
+            uint32_t i = pre;
 #pragma unroll
-            for (int b = 0; b < NS; b++)
+            for (int h = 0; h < NS; h += 2) {
+                uint32_t q[2][3];
 #pragma unroll
-                for (int ss = 0; ss < 3; ss++) {
-                    if ((sf >> (4 * b + ss)) & 1u) {
-                        const int zw = Structural<N>::zpos(ss) >> 1;
-                        static_assert(Structural<4>::zpos(0) & Structural<4>::zpos(1) & Structural<4>::zpos(2) & 1,
-                                      "4x4 structural coefficients sit in high halves");
-                        if (i < 64u) zp[b][zw] = __builtin_amdgcn_perm(res[i], zp[b][zw], 0x05040100u);  // res low -> high half
-                        i++;
-                    }
+                for (int d = 0; d < 2; d++) {
+#pragma unroll
+                    for (int ss = 0; ss < 3; ss++) q[d][ss] = res[i + ss];
+                    i += __popc(sf & (7u << (4 * (h + d))));
                 }
+#pragma unroll
+                for (int d = 0; d < 2; d++)
+#pragma unroll
+                    for (int ss = 0; ss < 3; ss++) asm volatile("" : "+v"(q[d][ss]));  // (all six reads issued before the first use)
+#pragma unroll
+                for (int d = 0; d < 2; d++) {
+                    const int b = h + d;
+                    const bool f0 = (sf >> (4 * b)) & 1u, f1 = (sf >> (4 * b + 1)) & 1u, f2 = (sf >> (4 * b + 2)) & 1u;
+                    const uint32_t v1 = f0 ? q[d][1] : q[d][0];
+                    const uint32_t v2 = f1 ? (f0 ? q[d][2] : q[d][1]) : v1;
+                    if (f0) zp[b][z0] = __builtin_amdgcn_perm(q[d][0], zp[b][z0], 0x05040100u);  // res low -> high half
+                    if (f1) zp[b][z1] = __builtin_amdgcn_perm(v1, zp[b][z1], 0x05040100u);
+                    if (f2) zp[b][z2] = __builtin_amdgcn_perm(v2, zp[b][z2], 0x05040100u);
+                }
+            }
             wave_sync();
+        } else {
+            // more than 64 requests (dense structural ties): rounds of 64, range-checked
+            for (uint32_t r0 = 0; r0 < total; r0 += 64) {
+                uint32_t m = sf, i = pre - r0;
+                while (m) {
+                    const int bit = __ffs(m) - 1;
+                    m &= m - 1;
+                    if (i < 64u) task[i] = (uint32_t(lane) << 4) | uint32_t(bit);
+                    i++;
+                }
+                wave_sync();
+                if (uint32_t(lane) < total - r0) res[lane] = task_y(task[lane]);
+                wave_sync();
+                // the owners take their results back: the flagged positions in bit order, each a
+                // constant register (the three structural coefficients are high halves of packed
+                // words), so no per-request select over every slot and coefficient
+                i = pre - r0;
+#pragma unroll
+                for (int b = 0; b < NS; b++)
+#pragma unroll
+                    for (int ss = 0; ss < 3; ss++) {
+                        if ((sf >> (4 * b + ss)) & 1u) {
+                            const int zw = Structural<N>::zpos(ss) >> 1;
+                            if (i < 64u) zp[b][zw] = __builtin_amdgcn_perm(res[i], zp[b][zw], 0x05040100u);  // res low -> high half
+                            i++;
+                        }
+                    }
+                wave_sync();
+            }
         }
         // whole-block requests (rare): all 16 coefficients in FP64, one per lane, four blocks a round
         const uint32_t wf = flags & 0x8888u;
@@ -1663,6 +1742,7 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
                 pb += __builtin_amdgcn_mbcnt_hi(uint32_t(bm >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(bm), 0u)) << k;
                 tb += uint32_t(__popcll(bm)) << k;
             }
+            wave_req += tb;
             for (uint32_t r0 = 0; r0 < tb; r0 += 4) {
                 uint32_t m = wf, j = pb - r0;
                 while (m) {
@@ -1701,10 +1781,9 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
             }
         }
     }
-    {  // statistics: FP64 requests of this wave (one store)
-        const uint32_t wsum = __builtin_amdgcn_readlane(wave_incl_scan_dpp(uint32_t(__popc(flags))), 63);
-        if (lane == 0) a.wave_fix[size_t(t) * 4 + wv] = wsum;
-    }
+    // statistics: FP64 requests of this wave (one store) -- the structural scan's total plus the
+    // whole-block count, both already in scalar registers
+    if (lane == 0) a.wave_fix[size_t(t) * 4 + wv] = wave_req;
     WSTAMP(3);
     asm volatile("; PHASE p3" ::: "memory");
 
@@ -1808,8 +1887,13 @@ __global__ __launch_bounds__(256, HIST ? IE_P_WAVES_HIST : IE_P_WAVES) void enco
     auto emit_slot = [&](int b) {  // slot b at its place in the (whole or pair) image
         if (!(IE_P_ABL & 2) && rb[b]) {
             const uint32_t p = reg_bit0 + (whole ? Sb[b] : Sb[b] - Sb[(b / PS) * PS]) + off[b];
-            if (a.tri && a.rle) emit_block3(smem, p, zp[b], blw[b]);
-            else emit_block2<N>(smem, p, zp[b], blw[b], a.rle);
+            if (a.tri && a.rle) {
+                // (wave-uniform: a slot whose every record has bl <= 8 takes the four-coefficient fields)
+                if (!__ballot((blw[b] & 0xFFu) > 8u)) emit_block4(p, zp[b], blw[b]);
+                else emit_block3(smem, p, zp[b], blw[b]);
+            } else {
+                emit_block2<N>(smem, p, zp[b], blw[b], a.rle);
+            }
         }
     };
     zero_img(whole ? Tw : S2);
