@@ -98,6 +98,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     if hasattr(L, "ie_decode_frames"):
         L.ie_decode_frames.argtypes = [vp, u8p, C.c_size_t, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int,
                                        u8p, C.c_size_t, C.c_size_t, u64p]
+    if hasattr(L, "ie_decode_images"):  # (absent from an older IE_LIB build under comparison)
+        L.ie_decode_images.restype = C.c_int
+        L.ie_decode_images.argtypes = [vp, u8p, C.c_size_t, u64p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int,
+                                       u8p, C.c_size_t, C.c_size_t, u64p]
     L.ie_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(C.c_void_p)]
     L.ie_host_free.argtypes = [vp, vp]
     L.ie_vstream_open.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, u8p, C.c_uint64,
@@ -497,6 +501,24 @@ class Codec:
         self._chk(self.L.ie_decode_frames(self.h, _ptr(stream), n, start_bit, w, h, nframes, int(rle), _ptr(out),
                                           stride, frame_pitch, C.byref(end)))
         return int(end.value)
+
+    def decode_images(self, streams, in_pitch: int, nbits, w: int, h: int, out, start_bit: int = 0, rle: bool = True,
+                      stride: int | None = None, frame_pitch: int | None = None) -> np.ndarray:
+        """Decode ``len(nbits)`` independent images in one set of launches (ie_decode_images):
+        image k's stream is the bits ``[0, nbits[k])`` of ``streams + k*in_pitch`` with its first
+        record at ``start_bit``; its pixels go to ``out + k*frame_pitch``.  ``streams``/``out``:
+        numpy arrays (host) or torch tensors (device).  Returns the end bits (uint64, one per
+        image); raises :class:`IEError` (``IE_EFORMAT``, the message names the image) when an
+        image's stream ends before its last block -- the other images are decoded all the same."""
+        stride = w if stride is None else stride
+        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        nb = np.ascontiguousarray(nbits, dtype=np.uint64)
+        eb = np.zeros(max(nb.size, 1), dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        self._chk(self.L.ie_decode_images(self.h, _ptr(streams), in_pitch, nb.ctypes.data_as(u64p), int(nb.size),
+                                          start_bit, w, h, int(rle), _ptr(out), stride, frame_pitch,
+                                          eb.ctypes.data_as(u64p)))
+        return eb[: nb.size]
 
     # ---- whole files (libie_host.so, include/ie_host.hpp)
     def _host_chk(self, r: int) -> int:

@@ -125,6 +125,13 @@ struct ie_ctx {
                                        // record count, [3] histogram ticket
     uint64_t* h_decres = nullptr;      // record decode results, pinned host memory the device writes
     uint64_t* d_decres = nullptr;      // directly ([0] end bit, [1] record total): no read-back copy
+    // ie_decode_images: [cap_imgres][2] the same pair per image, then [cap_imgres] the images'
+    // stream lengths on their way to d_imgbits (pinned, mapped: h_ / d_ are the two views)
+    uint64_t* h_imgres = nullptr;
+    uint64_t* d_imgres = nullptr;
+    size_t cap_imgres = 0;
+    uint64_t* d_imgbits = nullptr;     // [cap_imgbits] stream bits of every image (device)
+    size_t cap_imgbits = 0;
     uint16_t* d_hlut = nullptr;        // Huffman decode prefix table (32768 entries)
     size_t cap_hlut = 0;
     uint8_t* d_hout = nullptr;         // Huffman decode output staging (host destinations)
@@ -1619,6 +1626,8 @@ int ie_destroy(ie_ctx* c) {
     (void)hipFree(c->d_rpos);
     (void)hipFree(c->d_misc);
     if (c->h_decres) (void)hipHostFree(c->h_decres);
+    if (c->h_imgres) (void)hipHostFree(c->h_imgres);
+    if (c->d_imgbits) (void)hipFree(c->d_imgbits);
     (void)hipFree(c->d_hlut);
     (void)hipFree(c->d_hout);
     (void)hipFree(c->d_pix);
@@ -2518,17 +2527,18 @@ int finish_decode(ie_ctx* c, uint8_t* out, const uint8_t* dpix, bool out_dev, in
     return IE_OK;
 }
 
-// Chunk plan of a record span (span bits from the first record, nblocks records) and the
-// parse buffers it needs: fills a's chunking fields and scratch pointers, *levels = composition
-// levels.  The record stream's own fields (words, nbits, start_bit, dstart, total, end_out) are
-// the caller's.
 #ifndef IE_GOP_CAPC
 #define IE_GOP_CAPC 1  // 0: (A/B builds) gop decode chunks sized by the I-frame bound alone
 #endif
-int plan_records(ie_ctx* c, uint64_t span, uint64_t nblocks, ie::RecParseArgs& a, size_t* spec_at_out, int* levels_out,
-                 uint64_t cmax = uint64_t(1) << 15) {
+// Chunk plan of a record span (span bits from the first record, nblocks records).
+struct RecPlan {
+    uint64_t C;       // chunk bits
+    int nchunks;
+    size_t tab_rows;  // rows of D entries: the chunks' tables and every level's composites
+    int levels;
+};
+int plan_chunks(ie_ctx* c, uint64_t span, uint64_t nblocks, uint64_t cmax, RecPlan* plan) {
     const int n = c->n;
-    int r;
     // chunking: about R records per chunk (IE_DEC_R; default 24 for 4x4, 28 for 8x8: measured
     // with 32-table composition groups on 4K noise / mixed / gradient / flat frames and the
     // reference's ex1 / ex4 -- 4x4 against 16, 24, 32, 48: ex4 126 -> 115 us, mixed 197 -> 191 us,
@@ -2537,7 +2547,7 @@ int plan_records(ie_ctx* c, uint64_t span, uint64_t nblocks, ie::RecParseArgs& a
     // 24) so that every chunk's walks are short; C a multiple of 32, at least
     // 256 bits, at most 2^15 (16-bit record positions; a table wave's LDS -- the chunk's bits and
     // valid-header bitmap -- stays small)
-    const int G = ie::rec_group_chunks(n), D = ie::rec_entry_span(n);
+    const int G = ie::rec_group_chunks(n);
     static const char* rs = getenv("IE_DEC_R");
     const uint64_t recs = rs ? std::max<uint64_t>(1, strtoull(rs, nullptr, 10)) : (n == 4 ? 24 : 28);
     const uint64_t want = std::max<uint64_t>((nblocks + recs - 1) / recs, 1);
@@ -2557,7 +2567,22 @@ int plan_records(ie_ctx* c, uint64_t span, uint64_t nblocks, ie::RecParseArgs& a
     }
     if (levels > ie::kRecMaxLevels || nch > uint64_t(INT32_MAX))
         return fail(c, IE_EINVAL, "stream too long for one decode call");
-    const int nchunks = int(nch);
+    *plan = {C, int(nch), tab_rows, levels};
+    return IE_OK;
+}
+// The chunk plan and the parse buffers it needs: fills a's chunking fields and scratch pointers,
+// *levels = composition levels.  The record stream's own fields (words, nbits, start_bit, dstart,
+// total, end_out) are the caller's.
+int plan_records(ie_ctx* c, uint64_t span, uint64_t nblocks, ie::RecParseArgs& a, size_t* spec_at_out, int* levels_out,
+                 uint64_t cmax = uint64_t(1) << 15) {
+    const int n = c->n;
+    int r;
+    RecPlan pl{};
+    if ((r = plan_chunks(c, span, nblocks, cmax, &pl))) return r;
+    const int G = ie::rec_group_chunks(n), D = ie::rec_entry_span(n);
+    const uint64_t C = pl.C;
+    const size_t tab_rows = pl.tab_rows;
+    const int nchunks = pl.nchunks, levels = pl.levels;
     if ((r = ensure(c, c->d_rtab, c->cap_rtab, tab_rows * D))) return r;
     // d_walk (8-byte words): [nchunks / 2] in-workgroup record bases, [G / 2] top-level entries,
     // [nchunks / 2] chunk counts, [nchunks / 2] count-pass workgroup totals (a workgroup covers at
@@ -2764,6 +2789,161 @@ int ie_decode_frames(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bi
                      int use_rle, uint8_t* out, size_t stride, size_t frame_pitch, uint64_t* end_bit) {
     if (!c || !in || !out) return IE_EINVAL;
     return decode_frames_impl(c, in, len, start_bit, w, h, nframes, use_rle, out, stride, frame_pitch, end_bit, 0);
+}
+
+// A batch of independent images through ONE set of launches: every pass of the exact record parse
+// gains the image as its grid's y dimension (ie_decode.hip, the kernels' batch instantiations), so
+// the launch chain, the synchronisation and the result read are paid once.  One chunk plan for the
+// batch: C from the longest stream, nchunks its chunk count; a shorter stream's trailing chunks
+// hold no record.  Scratch is per image (tables + composites, position lists, walk arrays); a batch
+// whose scratch would pass kDecBatchBytes runs as sub-batches, one after another on the stream,
+// and the call still waits once.
+constexpr size_t kDecBatchBytes = size_t(1) << 30;
+int ie_decode_images(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64_t* nbits, int count, uint64_t start_bit,
+                     int w, int h, int use_rle, uint8_t* out, size_t stride, size_t frame_pitch, uint64_t* end_bits) {
+    if (!c || !in || !nbits || !out) return IE_EINVAL;
+    int r = check_dims(c, w, h, count);
+    if (r) return r;
+    if (stride < size_t(w)) return fail(c, IE_EINVAL, "stride < width");
+    if (count > 1 && frame_pitch < stride * size_t(h - 1) + size_t(w))
+        return fail(c, IE_EINVAL, "frame_pitch smaller than a frame");
+    uint64_t max_bits = 0;
+    for (int k = 0; k < count; k++) {
+        if (nbits[k] / 8 > in_pitch || nbits[k] > uint64_t(in_pitch) * 8)
+            return fail(c, IE_EINVAL, "image " + std::to_string(k) + ": nbits beyond its slot of in_pitch bytes");
+        if (start_bit > nbits[k]) return fail(c, IE_EINVAL, "image " + std::to_string(k) + ": start_bit beyond the stream");
+        max_bits = std::max(max_bits, nbits[k]);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int n = c->n;
+    const uint64_t nblocks = uint64_t(w / n) * (h / n);
+    RecPlan pl{};
+    if ((r = plan_chunks(c, max_bits - start_bit, nblocks, uint64_t(1) << 15, &pl))) return r;
+    const int G = ie::rec_group_chunks(n), D = ie::rec_entry_span(n);
+    const size_t nch = size_t(pl.nchunks);
+    const int seg = ie::rec_count_seg(uint32_t(pl.C));
+    const size_t nwg = (nch + 4 * size_t(seg) - 1) / (4 * size_t(seg));
+    // per image: table rows (a multiple of 8 entries, so every image's tables start 16-byte
+    // aligned), kRecPosCap positions per chunk, and 32-bit words for lbase, cnt, wgsum and E
+    const size_t img_tab = (pl.tab_rows * size_t(D) + 7) / 8 * 8;
+    const size_t img_u32 = 2 * nch + nwg + size_t(G);
+    const size_t img_bytes = img_tab * 2 + nch * ie::kRecPosCap * 2 + img_u32 * 4;
+    size_t batch = std::max<size_t>(1, kDecBatchBytes / img_bytes);
+    if (const char* eb = getenv("IE_DEC_BATCH_MAX"))  // (read on every call: a limit in images, only ever lower)
+        if (atoi(eb) > 0) batch = std::min<size_t>(batch, size_t(atoi(eb)));
+    batch = std::min<size_t>(batch, size_t(count));
+    if ((r = ensure(c, c->d_rtab, c->cap_rtab, batch * img_tab))) return r;
+    if ((r = ensure(c, c->d_rpos, c->cap_rpos, batch * nch * ie::kRecPosCap))) return r;
+    if ((r = ensure(c, c->d_walk, c->cap_walk, (batch * img_u32 + 1) / 2 + 1))) return r;
+    if ((r = ensure(c, c->d_imgbits, c->cap_imgbits, size_t(count)))) return r;
+    if (c->cap_imgres < size_t(count)) {
+        if (c->h_imgres) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipHostFree(c->h_imgres));
+            c->h_imgres = nullptr;
+            c->cap_imgres = 0;
+        }
+        const size_t cap = std::max<size_t>(size_t(count), 16);
+        void* hp = nullptr;
+        HIPCHK(c, hipHostMalloc(&hp, cap * 3 * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent));
+        c->h_imgres = static_cast<uint64_t*>(hp);
+        void* dp = nullptr;
+        HIPCHK(c, hipHostGetDevicePointer(&dp, hp, 0));
+        c->d_imgres = static_cast<uint64_t*>(dp);
+        c->cap_imgres = cap;
+    }
+    // the stream lengths: through pinned memory into a device array (every workgroup reads its
+    // image's; a read of host memory per workgroup would cost more than the copy)
+    uint64_t* h_bits = c->h_imgres + 2 * c->cap_imgres;
+    std::memcpy(h_bits, nbits, size_t(count) * sizeof(uint64_t));
+    HIPCHK(c, hipMemcpyAsync(c->d_imgbits, h_bits, size_t(count) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    // streams: device slots that are 16-byte aligned, 16-byte pitched are read in place (16-byte
+    // vector loads of whole aligned groups inside [0, nbits[k]), single words up to the one holding
+    // the last bit -- inside the slot, as in_pitch is a multiple of 4 -- and the bits at or past
+    // nbits[k] are cleared by the kernels); anything else is staged into such slots, zero padded
+    const bool in_dev = is_device_ptr(in);
+    const uint8_t* words = in;
+    size_t pitch = in_pitch;
+    if (!in_dev || (reinterpret_cast<uintptr_t>(in) & 15u) || (in_pitch & 15u)) {
+        const size_t max_bytes = size_t((max_bits + 7) / 8);
+        pitch = (max_bytes + 15) / 16 * 16 + 16;
+        if ((r = ensure(c, c->d_dec, c->cap_dec, pitch * size_t(count)))) return r;
+        HIPCHK(c, hipMemsetAsync(c->d_dec, 0, pitch * size_t(count), c->stream));
+        if (in_dev) {
+            HIPCHK(c, hipMemcpy2DAsync(c->d_dec, pitch, in, in_pitch, std::min(max_bytes, in_pitch), size_t(count),
+                                       hipMemcpyDeviceToDevice, c->stream));
+        } else {
+            for (int k = 0; k < count; k++)
+                if (nbits[k])
+                    HIPCHK(c, hipMemcpyAsync(c->d_dec + size_t(k) * pitch, in + size_t(k) * in_pitch,
+                                             size_t((nbits[k] + 7) / 8), hipMemcpyHostToDevice, c->stream));
+        }
+        words = c->d_dec;
+    }
+    const bool out_dev = is_device_ptr(out);
+    uint8_t* dpix = out;
+    if (!out_dev) {
+        const size_t pix_bytes = size_t(count - 1) * frame_pitch + stride * size_t(h - 1) + size_t(w);
+        if ((r = ensure(c, c->d_pix, c->cap_pix, pix_bytes))) return r;
+        dpix = c->d_pix;
+    }
+    ie::DecArgs da{};
+    da.nframes = 1;
+    da.bx = w / n;
+    da.by = h / n;
+    da.rle = use_rle ? 1 : 0;
+    da.stride = stride;
+    da.frame_pitch = frame_pitch;
+    da.tab = c->d_tab;
+    ie::RecParseArgs pa{};
+    pa.start_bit = start_bit;
+    pa.rle = da.rle;
+    pa.C = uint32_t(pl.C);
+    pa.nchunks = pl.nchunks;
+    pa.seg = seg;
+    pa.ticket = reinterpret_cast<unsigned*>(c->d_misc + 1);
+    pa.tab = c->d_rtab;
+    pa.pos = c->d_rpos;
+    uint32_t* u32 = reinterpret_cast<uint32_t*>(c->d_walk);
+    pa.lbase = u32;
+    pa.cnt = u32 + batch * nch;
+    pa.wgsum = u32 + 2 * batch * nch;
+    pa.E = u32 + 2 * batch * nch + batch * nwg;
+    pa.img_words = pitch / 4;
+    pa.img_tab = img_tab;
+    pa.img_chunks = uint32_t(nch);
+    pa.img_wg = uint32_t(nwg);
+    pa.img_E = uint32_t(G);
+    int levels = 0;
+    for (size_t k0 = 0; k0 < size_t(count); k0 += batch) {  // (sub-batches share the scratch: stream order)
+        const int m = int(std::min(batch, size_t(count) - k0));
+        pa.words = reinterpret_cast<const uint32_t*>(words + k0 * pitch);
+        pa.img_nbits = c->d_imgbits + k0;
+        pa.end_out = c->d_imgres + 2 * k0;
+        pa.total = c->d_imgres + 2 * k0 + 1;
+        da.out = dpix + k0 * frame_pitch;
+        levels = ie::launch_rec_parse_decode_images(pa, da, n, m, c->stream);
+        if (levels < 0) return fail(c, IE_EINVAL, "stream too long for one decode call");
+        HIPCHK(c, hipGetLastError());
+    }
+    c->last_chunks = pl.nchunks;
+    c->last_groups = levels;
+    c->last_spec = 0;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // (every image's last chunk wrote its record total; its end bit is read only when that total
+    // covers the last block, whose decode wrote it)
+    int bad = -1;
+    for (int k = count - 1; k >= 0; k--) {
+        const uint64_t end = c->h_imgres[2 * k], total = c->h_imgres[2 * k + 1];
+        const bool ok = total >= nblocks && end <= nbits[k];
+        if (!ok) bad = k;
+        if (end_bits) end_bits[k] = ok ? end : UINT64_MAX;
+        if (ok && !out_dev)
+            HIPCHK(c, hipMemcpy2D(out + size_t(k) * frame_pitch, stride, dpix + size_t(k) * frame_pitch, stride, size_t(w),
+                                  size_t(h), hipMemcpyDeviceToHost));
+    }
+    if (bad >= 0) return fail(c, IE_EFORMAT, "image " + std::to_string(bad) + ": stream ends before the last block");
+    return IE_OK;
 }
 
 // Video decode with P-frames (VideoDecoder.cpp:28-58, Frame.cpp:47-127): frame by frame, each

@@ -343,10 +343,16 @@ __device__ __forceinline__ void stage_u16(uint16_t* S, const uint16_t* T, int n,
     for (int i = head + tid; i < n; i += kTPB) S[i] = T[i];
 }
 
-template <int D, int G>
-__global__ __launch_bounds__(kTPB) void compose_kernel(uint16_t* tab, int n, uint16_t* comp) {
+// B (image batch): blockIdx.y = the image, whose tables and composites lie img entries after the
+// previous image's.
+template <int D, int G, bool B = false>
+__global__ __launch_bounds__(kTPB) void compose_kernel(uint16_t* tab, int n, uint16_t* comp, size_t img) {
     __shared__ __attribute__((aligned(16))) uint16_t S[G * D];
     const int tid = threadIdx.x, g = blockIdx.x;
+    if constexpr (B) {
+        tab += size_t(blockIdx.y) * img;
+        comp += size_t(blockIdx.y) * img;
+    }
     const int k0 = g * G, nk = min(G, n - k0);
     uint16_t* T = tab + size_t(k0) * D;
     stage_u16(S, T, nk * D, tid);
@@ -379,9 +385,14 @@ __global__ __launch_bounds__(kTPB) void compose_kernel(uint16_t* tab, int n, uin
 // a device-wide fence in every composing workgroup).  (A segmented chase -- every entry through
 // each of 8 segments, then entry 0 through the segment maps -- measured slower here and in
 // compose_kernel: 9.2 -> 11.6 and 15.2 -> 18.1 us.)
-template <int D, int G>
-__global__ __launch_bounds__(kTPB) void compose_top_kernel(const uint16_t* comp, int ng, uint32_t* E) {
+template <int D, int G, bool B = false>
+__global__ __launch_bounds__(kTPB) void compose_top_kernel(const uint16_t* comp, int ng, uint32_t* E, size_t img,
+                                                           uint32_t img_E) {
     __shared__ __attribute__((aligned(16))) uint16_t S[G * D];
+    if constexpr (B) {  // (every image's stream starts at its own first record: entry 0)
+        comp += size_t(blockIdx.y) * img;
+        E += size_t(blockIdx.y) * img_E;
+    }
     stage_u16(S, comp, ng * D, threadIdx.x);
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -395,9 +406,11 @@ __global__ __launch_bounds__(kTPB) void compose_top_kernel(const uint16_t* comp,
 
 // The composition levels over n tables: level l+1's tables are level l's composites, until at
 // most G remain (the top chase).  lvl[l] receives level l's table array; returns the number of
-// levels, or -1 past kRecMaxLevels.
-template <int D, int G>
-int launch_compose(uint16_t* tab, int n, uint32_t* E, unsigned* ticket, uint16_t** lvl, hipStream_t s) {
+// levels, or -1 past kRecMaxLevels.  B: `images` batches of n tables each, img entries (E: img_E
+// words) apart, composed by the same launches (lvl[] receives image 0's arrays).
+template <int D, int G, bool B = false>
+int launch_compose(uint16_t* tab, int n, uint32_t* E, unsigned* ticket, uint16_t** lvl, hipStream_t s, int images = 1,
+                   size_t img = 0, uint32_t img_E = 0) {
     int cur = n, levels = 0;
     uint16_t* arr = tab;
     for (;;) {
@@ -406,10 +419,10 @@ int launch_compose(uint16_t* tab, int n, uint32_t* E, unsigned* ticket, uint16_t
         if (levels >= kRecMaxLevels) return -1;
         lvl[levels] = arr;
         uint16_t* comp = arr + size_t(cur) * D;
-        hipLaunchKernelGGL((compose_kernel<D, G>), dim3(ng), dim3(kTPB), 0, s, arr, cur, comp);
+        hipLaunchKernelGGL((compose_kernel<D, G, B>), dim3(ng, images), dim3(kTPB), 0, s, arr, cur, comp, img);
         levels++;
         if (top) {
-            hipLaunchKernelGGL((compose_top_kernel<D, G>), dim3(1), dim3(kTPB), 0, s, comp, ng, E);
+            hipLaunchKernelGGL((compose_top_kernel<D, G, B>), dim3(1, images), dim3(kTPB), 0, s, comp, ng, E, img, img_E);
             (void)ticket;
             return levels;
         }
@@ -443,10 +456,50 @@ __device__ __forceinline__ uint32_t table_entry(const uint32_t* E, uint16_t* con
 }
 
 // the chunk's entry offset (record parse): composed tables, or the predecessor's speculative exit
-template <int N>
+template <int N, bool B = false>
 __device__ __forceinline__ uint32_t rec_chunk_entry(const RecParseArgs& a, int k) {
+    if constexpr (B) {
+        // table_entry with the levels unrolled: lvl[] is indexed by constants only, so the rebased
+        // copy of the arguments (rec_image) stays in registers (a run-time index puts all of it in
+        // scratch).  lvl[] itself stays image 0's: this image's arrays lie img entries after.
+        constexpr int D = RecGeom<N>::D, G = RecGeom<N>::G;
+        const size_t img = size_t(blockIdx.y) * a.img_tab;
+        int u = k;
+        for (int l = 0; l < a.levels; l++) u /= G;
+        uint32_t x = a.E[u];
+#pragma unroll
+        for (int l = kRecMaxLevels - 1; l >= 0; l--) {
+            if (l < a.levels) {
+                int ul = k;
+#pragma unroll
+                for (int m = 0; m < l; m++) ul /= G;
+                x = a.lvl[l][img + size_t(ul) * D + x];
+            }
+        }
+        return x;
+    }
     if (a.spec) return k ? a.spec[k - 1] : 0u;
     return table_entry<RecGeom<N>::D, RecGeom<N>::G>(a.E, a.lvl, a.levels, k);
+}
+
+// Image batch: the launch's arguments rebased to image blockIdx.y -- its stream, its length and its
+// scratch -- so that every pass below runs on it as on a single stream.  (lvl[] is left alone: see
+// rec_chunk_entry.)
+template <bool B>
+__device__ __forceinline__ void rec_image(RecParseArgs& a) {
+    if constexpr (B) {
+        const size_t y = blockIdx.y;
+        a.words += y * a.img_words;
+        a.nbits = a.img_nbits[y];
+        a.tab += y * a.img_tab;
+        a.E += y * a.img_E;
+        a.pos += y * a.img_chunks * kRecPosCap;
+        a.cnt += y * a.img_chunks;
+        a.lbase += y * a.img_chunks;
+        a.wgsum += y * a.img_wg;
+        a.total += 2 * y;
+        a.end_out += 2 * y;
+    }
 }
 
 // The record span of a launch: [start, nbits) -- the host's, or, device-chained (a.dstart), from
@@ -549,9 +602,10 @@ __host__ __device__ constexpr int rec_table2_words(uint32_t C, int D, int tm, in
            2 * ((tm * (D + 1) + 1) / 2) + tm + (tm * int(C >> 5) + 2) / 2;
 }
 
-template <int N>
+template <int N, bool B = false>
 __global__ __launch_bounds__(64) void rec_table2_kernel(RecParseArgs a) {
     constexpr int D = RecGeom<N>::D, D1 = D + 1;
+    rec_image<B>(a);
     extern __shared__ __attribute__((aligned(16))) uint32_t Ls[];
     const int lane = threadIdx.x, tm = a.tm;
     const int k0 = blockIdx.x * tm;
@@ -813,10 +867,11 @@ __global__ __launch_bounds__(kTPB) void rec_spec_kernel(RecParseArgs a) {
 // its true records from its entry (the prefix maps applied to its top-level entry), storing up to
 // kRecPosCap record positions (relative to the chunk's first word) and the count; the workgroup
 // then scans its 4 * seg chunks' counts (records before each chunk among them, and their total).
-template <int N>
+template <int N, bool B = false>
 __global__ __launch_bounds__(kTPB) void rec_count_kernel(RecParseArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t Lall[];
     __shared__ alignas(8) uint32_t scratch[8];
+    rec_image<B>(a);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int seg = a.seg;
     const int k0 = (blockIdx.x * 4 + wv) * seg;  // this wave's first chunk
@@ -833,7 +888,7 @@ __global__ __launch_bounds__(kTPB) void rec_count_kernel(RecParseArgs a) {
     }
     const int k = k0 + lane;
     const bool mine = lane < m;
-    const uint32_t x = mine ? rec_chunk_entry<N>(a, k) : 0u;
+    const uint32_t x = mine ? rec_chunk_entry<N, B>(a, k) : 0u;
     wave_sync();
     uint32_t R = 0;
     if (mine) {
@@ -870,10 +925,12 @@ __global__ __launch_bounds__(kTPB) void rec_count_kernel(RecParseArgs a) {
 // chunk holds about 32), one record per lane, so the FP64 IDCT -- the pass's cost -- runs on full
 // waves.  Record positions come from the count pass (relative to each chunk's first word; chunk j
 // of the wave starts j * C bits after chunk 0, C a multiple of 32).
-template <int N>
+template <int N, bool B = false>
 __global__ __launch_bounds__(64 * kRecWPB) void rec_decode_kernel(RecParseArgs a, DecArgs d) {
     constexpr int D = RecGeom<N>::D;
     constexpr int P = kDecChunks;
+    rec_image<B>(a);
+    if constexpr (B) d.out += size_t(blockIdx.y) * d.frame_pitch;  // (d.nframes = 1: block index < bx * by)
     extern __shared__ __attribute__((aligned(16))) uint32_t dyn_all[];  // per wave: the P chunks' bits + D + 64
     const const_f64 sR = (const_f64)(d.tab->R);
     const const_f64 sq = (const_f64)(d.tab->qd);
@@ -932,7 +989,7 @@ __global__ __launch_bounds__(64 * kRecWPB) void rec_decode_kernel(RecParseArgs a
     // at a time
     uint64_t gi = first;
     for (int j = 0; j < m; j++) {
-        uint32_t p = s0 + uint32_t(j) * a.C + rec_chunk_entry<N>(a, k0 + j);
+        uint32_t p = s0 + uint32_t(j) * a.C + rec_chunk_entry<N, B>(a, k0 + j);
         const uint32_t wend = uint32_t(min<uint64_t>(s0 + uint64_t(j + 1) * a.C, sat_sub(sp.nbits, lbase0)));
         while (p < wend && gi < nblocks) {
             uint32_t mine = 0, n = 0;
@@ -975,27 +1032,31 @@ size_t rec_decode_lds(uint32_t C, int n) {
     return size_t(rec_decode_stream_words(uint32_t(kDecChunks) * C, rec_entry_span(n))) * 4 * kRecWPB;
 }
 
-int launch_rec_parse_decode(RecParseArgs a, const DecArgs& d, int n, hipStream_t s) {
+// The five passes; B: over `images` independent streams, the image as every grid's y dimension.
+template <int N, bool B>
+int launch_rec_parse_decode_t(RecParseArgs a, const DecArgs& d, int images, hipStream_t s) {
     if (a.nchunks <= 0) return 0;
     const int nb = (a.nchunks + kRecWPB * kDecChunks - 1) / (kRecWPB * kDecChunks);  // decode blocks
-    const int nt = (a.nchunks + RecGeom<4>::M - 1) / RecGeom<4>::M;  // table waves (M chunks each)
-    (void)nt;
-    rec_table_geometry(a.C, n, &a.tm, &a.hbits);
+    rec_table_geometry(a.C, N, &a.tm, &a.hbits);
     const int nt2 = (a.nchunks + a.tm - 1) / a.tm;
-    const size_t l2 = size_t(rec_table2_words(a.C, rec_entry_span(n), a.tm, a.hbits)) * 4;
-    if (n == 4) hipLaunchKernelGGL((rec_table2_kernel<4>), dim3(nt2), dim3(64), l2, s, a);
-    else hipLaunchKernelGGL((rec_table2_kernel<8>), dim3(nt2), dim3(64), l2, s, a);
-    const int levels = (n == 4) ? launch_compose<RecGeom<4>::D, RecGeom<4>::G>(a.tab, a.nchunks, a.E, a.ticket + 1, a.lvl, s)
-                                : launch_compose<RecGeom<8>::D, RecGeom<8>::G>(a.tab, a.nchunks, a.E, a.ticket + 1, a.lvl, s);
+    const size_t l2 = size_t(rec_table2_words(a.C, RecGeom<N>::D, a.tm, a.hbits)) * 4;
+    hipLaunchKernelGGL((rec_table2_kernel<N, B>), dim3(nt2, images), dim3(64), l2, s, a);
+    const int levels = launch_compose<RecGeom<N>::D, RecGeom<N>::G, B>(a.tab, a.nchunks, a.E, a.ticket + 1, a.lvl, s, images,
+                                                                       a.img_tab, a.img_E);
     if (levels < 0) return -1;
     a.levels = levels;
     const int nbc = (a.nchunks + 4 * a.seg - 1) / (4 * a.seg);
     const size_t lc = size_t(rec_count_wave_words(a.C, a.seg)) * 4 * 4;
-    if (n == 4) hipLaunchKernelGGL((rec_count_kernel<4>), dim3(nbc), dim3(kTPB), lc, s, a);
-    else hipLaunchKernelGGL((rec_count_kernel<8>), dim3(nbc), dim3(kTPB), lc, s, a);
-    if (n == 4) hipLaunchKernelGGL((rec_decode_kernel<4>), dim3(nb), dim3(64 * kRecWPB), rec_decode_lds(a.C, 4), s, a, d);
-    else hipLaunchKernelGGL((rec_decode_kernel<8>), dim3(nb), dim3(64 * kRecWPB), rec_decode_lds(a.C, 8), s, a, d);
+    hipLaunchKernelGGL((rec_count_kernel<N, B>), dim3(nbc, images), dim3(kTPB), lc, s, a);
+    hipLaunchKernelGGL((rec_decode_kernel<N, B>), dim3(nb, images), dim3(64 * kRecWPB), rec_decode_lds(a.C, N), s, a, d);
     return levels;
+}
+
+int launch_rec_parse_decode(RecParseArgs a, const DecArgs& d, int n, hipStream_t s) {
+    return n == 4 ? launch_rec_parse_decode_t<4, false>(a, d, 1, s) : launch_rec_parse_decode_t<8, false>(a, d, 1, s);
+}
+int launch_rec_parse_decode_images(RecParseArgs a, const DecArgs& d, int n, int images, hipStream_t s) {
+    return n == 4 ? launch_rec_parse_decode_t<4, true>(a, d, images, s) : launch_rec_parse_decode_t<8, true>(a, d, images, s);
 }
 
 __global__ void gop_init_kernel(uint64_t* pos, uint64_t* tot, int n, uint64_t start) {

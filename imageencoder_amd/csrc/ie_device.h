@@ -246,6 +246,18 @@ struct RecParseArgs {
     // `span` bits after it (start_bit is then unused); chunks past the span's end hold no record
     const uint64_t* dstart;
     uint64_t start_add, span;
+    // image batch (ie_decode_images: the kernels' batch instantiations, blockIdx.y = the image; the
+    // single-stream launches never read these).  Every image is a stream of its own from start_bit
+    // with one chunk plan (C, nchunks: the longest stream's; a shorter stream's trailing chunks see
+    // no stream bits and hold no record).  Image y reads words + y * img_words, is img_nbits[y] bits
+    // long (nbits is then unused) and owns its scratch at the strides below; its total / end_out
+    // are total[2 * y] / end_out[2 * y], its pixels DecArgs::out + y * frame_pitch (nframes = 1).
+    const uint64_t* img_nbits;  // device [images]
+    uint64_t img_words;         // 32-bit words between the images' streams
+    uint64_t img_tab;           // 16-bit entries between the images' tab (and lvl[]) arrays
+    uint32_t img_chunks;        // entries between the images' cnt / lbase (x kRecPosCap: pos)
+    uint32_t img_wg;            // entries between the images' wgsum
+    uint32_t img_E;             // entries between the images' E
 };
 // Table-wave geometry for chunks of C bits: chunks per wave (tm) and log2 claim slots (hbits).
 void rec_table_geometry(uint32_t C, int n, int* tm, int* hbits);
@@ -255,6 +267,9 @@ size_t rec_decode_lds(uint32_t C, int n);
 int rec_count_seg(uint32_t C);
 // Returns the number of composition levels (< 0: too many chunks).
 int launch_rec_parse_decode(RecParseArgs a, const DecArgs& d, int n, hipStream_t s);
+// The same five passes over `images` independent streams (the img_ fields set; d.nframes = 1,
+// image y's pixels at d.out + y * d.frame_pitch): every grid gains the image as its y dimension.
+int launch_rec_parse_decode_images(RecParseArgs a, const DecArgs& d, int n, int images, hipStream_t s);
 // the speculative form (a.spec, a.fail set): speculative walks, verifying count pass, decode
 void launch_rec_spec_decode(const RecParseArgs& a, const DecArgs& d, int n, hipStream_t s);
 

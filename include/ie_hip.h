@@ -280,6 +280,35 @@ int ie_decode_frames(ie_ctx* ctx, const uint8_t* in, size_t len, uint64_t start_
                      int nframes, int use_rle, uint8_t* out, size_t stride, size_t frame_pitch,
                      uint64_t* end_bit);
 
+/* Decode `count` INDEPENDENT images of w x h in one set of launches (the inverse of
+ * ie_encode_images). Image k's stream is the bits [0, nbits[k]) of in + k*in_pitch, its first
+ * record at start_bit (the same for every image: the settings header is the same); bits of the
+ * slot at or past nbits[k] are ignored, whatever they hold. Image k's pixels go to
+ * out + k*frame_pitch, row r at + r*stride. nbits: host array. in/out: host or device.
+ * end_bits (host, optional, [count]): the bit after image k's last record, UINT64_MAX for an
+ * image whose stream ends before its last block.
+ *  - IE_EINVAL: the checks of ie_decode_frames (dimensions, stride, frame_pitch when count > 1),
+ *    count < 1, nbits[k] > 8*in_pitch, start_bit > nbits[k].
+ *  - One synchronisation per call: every image's record total and end bit come back in one read.
+ *  - A truncated image k (fewer records than blocks, or its last record past nbits[k]) makes the
+ *    call return IE_EFORMAT, ie_last_error naming the lowest such k, with end_bits[k] =
+ *    UINT64_MAX; every other image's pixels and end bit are delivered as by a successful call
+ *    (host and device out alike; the truncated image's pixels are unspecified).
+ *  - A device `in` that is 16-byte aligned with in_pitch a multiple of 16 is read in place;
+ *    anything else (host memory, another pitch or base) is first copied into such slots on the
+ *    device, from host memory only the ceil(nbits[k]/8) bytes of every image.
+ *  - Always the exact parse: ie_set_exact_parse(ctx, 0) does not affect this call, and
+ *    ie_last_decode_spec returns 0 after it.  ie_last_decode_info then reports the chunks PER IMAGE
+ *    (one chunk plan serves the batch: chunk length from the longest stream) and the composition
+ *    levels.
+ *  - Scratch is per image (about 23 MB for a 3840x2160 4x4 image).  A batch whose scratch would
+ *    exceed 1 GiB runs as sub-batches one after another, still with one synchronisation at the
+ *    end; the environment variable IE_DEC_BATCH_MAX (read on every call) lowers the sub-batch
+ *    size in images further. */
+int ie_decode_images(ie_ctx* ctx, const uint8_t* in, size_t in_pitch, const uint64_t* nbits, int count,
+                     uint64_t start_bit, int w, int h, int use_rle,
+                     uint8_t* out, size_t stride, size_t frame_pitch, uint64_t* end_bits);
+
 /* Video payload with P-frames (VideoDecoder.cpp:28-58, Frame.cpp:47-127, Block.cpp:441-496): frame f
  * an I-frame when f % gop == 0 (decoded as ie_decode_frames), otherwise a P-frame: its motion vectors
  * (bits_needed(merange) bits each), the previous decoded frame's blocks at the clamped vectors copied
@@ -290,7 +319,8 @@ int ie_decode_gop(ie_ctx* ctx, const uint8_t* in, size_t len, uint64_t start_bit
                   int gop, int merange, int use_rle, int motioncomp, uint8_t* out, size_t stride,
                   size_t frame_pitch, uint64_t* end_bit);
 
-/* Chunks and composition levels of the last ie_decode_frames call's exact parse (diagnostics: the
+/* Chunks and composition levels of the last ie_decode_frames call's exact parse (after
+ * ie_decode_images: the chunks per image) (diagnostics: the
  * stream is cut into chunks of about 32 (4x4) / 16 (8x8) records, each tabulated over every entry
  * offset; the tables are composed G at a time, level after level). */
 int ie_last_decode_info(ie_ctx* ctx, int* chunks, int* levels);
