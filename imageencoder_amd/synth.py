@@ -8,6 +8,9 @@ or a GPU can reproduce the same bytes.  Two generators:
 * ``mixed``   (M): 64x64 tiles whose kind is ``splitmix64(seed ^ TILE_SALT, tile) % 3``:
   0 = flat 128 (all-zero blocks, the ``ffs(0)`` path), 1 = slow gradient + [-2, 2] noise,
   2 = uniform noise.
+
+``frames`` also builds whole videos: panning (P) and the constructed P-frame contents of
+``_pattern_frames`` (static, flat, stripes, checkerboard, known translation).
 """
 from __future__ import annotations
 
@@ -55,10 +58,59 @@ def frame(kind: str, w: int, h: int, seed: int = DEFAULT_SEED) -> np.ndarray:
     raise ValueError(f"unknown synthetic kind {kind!r}")
 
 
+SHIFTS = {"shiftA": (5, -3), "shiftB": (-17, 9)}  # true motion (dx, dy) per frame of the "shift" kinds
+
+
+def smooth(w: int, h: int, seed: int = DEFAULT_SEED, k: int = 16) -> np.ndarray:
+    """A k x k box sum of uniform noise stretched back over the 8-bit range: a picture whose SAD
+    against a displaced copy of itself grows with the displacement over about k px, so a pattern
+    search can descend to the true motion (integer arithmetic only)."""
+    u = uniform(w + k, h + k, seed).astype(np.int64)
+    s = np.zeros((h + k + 1, w + k + 1), dtype=np.int64)
+    s[1:, 1:] = u.cumsum(axis=0).cumsum(axis=1)
+    box = s[k: k + h, k: k + w] - s[:h, k: k + w] - s[k: k + h, :w] + s[:h, :w]
+    return np.clip(128 + (8 * box - 1020 * k * k) // (k * k), 0, 255).astype(np.uint8)
+
+
+PATTERNS = ("static", "flat128", "flat0255", "stripesV", "stripesH", "checker") + tuple(SHIFTS)
+
+
+def _pattern_frames(kind: str, w: int, h: int, count: int, seed: int) -> np.ndarray:
+    """The constructed P-frame contents: SAD ties, saturation, five-bit records, known motion."""
+    yy, xx = np.mgrid[0:h, 0:w]
+    out = np.empty((count, h, w), dtype=np.uint8)
+    if kind == "static":      # every frame the same uniform picture
+        out[:] = uniform(w, h, seed)
+    elif kind == "flat128":   # every candidate of every search ties
+        out[:] = 128
+    elif kind == "flat0255":  # frame f is constant 0 (f even) or 255 (f odd)
+        out[:] = (np.arange(count) % 2 * 255).astype(np.uint8)[:, None, None]
+    elif kind in ("stripesV", "stripesH"):  # 0/255 stripes of period 8 px, moving 4 px per frame
+        c = xx if kind == "stripesV" else yy
+        for f in range(count):
+            out[f] = ((c + 4 * f) // 4 % 2 * 255).astype(np.uint8)
+    elif kind == "checker":   # 1-px 0/255 checkerboard, inverted every frame
+        for f in range(count):
+            out[f] = ((xx + yy + f) % 2 * 255).astype(np.uint8)
+    elif kind in SHIFTS:      # frame f (x, y) = frame f - 1 (x + dx, y + dy): windows of one canvas
+        dx, dy = SHIFTS[kind]
+        n = count - 1
+        base = smooth(w + abs(dx) * n, h + abs(dy) * n, seed)
+        ox, oy = (0 if dx > 0 else -dx * n), (0 if dy > 0 else -dy * n)
+        for f in range(count):
+            out[f] = base[oy + dy * f: oy + dy * f + h, ox + dx * f: ox + dx * f + w]
+    else:
+        raise ValueError(f"unknown pattern kind {kind!r}")
+    return out
+
+
 def frames(kind: str, w: int, h: int, count: int, seed: int = DEFAULT_SEED) -> np.ndarray:
     """``count`` distinct frames (seed + frame index), shape (count, h, w).  Kind "P" (panning):
     windows of one larger "mixed" picture moving by (3, 2) px per frame plus +-2 noise -- content
-    a motion search can follow (the P-frame tests)."""
+    a motion search can follow (the P-frame tests).  The kinds of ``_pattern_frames`` are whole
+    videos built to reach one P-frame path each."""
+    if kind in PATTERNS:
+        return _pattern_frames(kind, w, h, count, seed)
     out = np.empty((count, h, w), dtype=np.uint8)
     if kind in ("P", "panning"):
         base = mixed(w + 3 * count + 8, h + 2 * count + 8, seed).astype(np.int64)

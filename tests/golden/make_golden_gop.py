@@ -81,6 +81,37 @@ def cases():
     add("gopU8x8x3_g3_m16", "U", 8, 8, 3, S + 104, 3, 16)        # no macroblock at all
     # full HD: pinned by md5
     add("gopP1080x3_g3_m16", "P", 1920, 1080, 3, S + 200, 3, 16)
+    # contents built for the search's tie rule (later candidates win, the own position skipped),
+    # for clamped candidates, five-bit records, wide records and saturation (synth._pattern_frames)
+    add("gopstatic64x48x5_g2_m8_dc", "static", 64, 48, 5, S + 110, 2, 8, matrix="matrix4_dc4096.txt")
+    add("gopstatic64x48x5_g5_m8", "static", 64, 48, 5, S + 110, 5, 8)
+    add("gopflat128_64x48x4_g4_m8", "flat128", 64, 48, 4, S + 111, 4, 8)
+    add("gopflat128_48x32x4_g4_m5", "flat128", 48, 32, 4, S + 111, 4, 5)
+    add("gopflat0255_64x48x5_g5_m3", "flat0255", 64, 48, 5, S + 112, 5, 3)
+    add("gopflat0255_48x32x4_g4_m8_q2", "flat0255", 48, 32, 4, S + 112, 4, 8, matrix="matrix4_2.txt")
+    add("gopstripesV64x48x5_g5_m8", "stripesV", 64, 48, 5, S + 113, 5, 8)
+    add("gopstripesV48x32x4_g2_m2", "stripesV", 48, 32, 4, S + 113, 2, 2)
+    add("gopstripesH64x48x5_g5_m8", "stripesH", 64, 48, 5, S + 114, 5, 8)
+    add("gopstripesH48x32x4_g4_m5", "stripesH", 48, 32, 4, S + 114, 4, 5)
+    add("gopchecker64x48x5_g5_m8", "checker", 64, 48, 5, S + 115, 5, 8)
+    add("gopchecker48x32x4_g4_m3_norle", "checker", 48, 32, 4, S + 115, 4, 3, rle=0)
+    add("gopshiftA64x48x5_g5_m8", "shiftA", 64, 48, 5, S + 116, 5, 8)
+    add("gopshiftB64x48x5_g5_m40", "shiftB", 64, 48, 5, S + 117, 5, 40)
+    # Candidates beyond int16 wrap before they are clamped (ImageBase.cpp:253-254).  The reference
+    # cannot be asked at merange 20000 or 32767: it materialises the whole pattern tree, 9 ** 14
+    # nodes there (algo.cpp:119-139), and dies.  The same wrap at a merange it can build: a frame
+    # 32752 px wide, where macroblock column 32736 + radius 32 = 32768 wraps to -32768 and clamps
+    # to column 0 (pinned by md5).  On flat content every candidate ties, so the wrapped one, not
+    # skipped, wins where a clamped one would be; on the translated picture its SAD differs.  (A
+    # restatement without the int16 casts misses both md5s; noise-like content would not tell.)
+    # merange 128 is the deepest tree kept here (9 ** 7 nodes).
+    add("gopflat128_32752x16x3_g3_m64", "flat128", 32752, 16, 3, S + 118, 3, 64)
+    add("gopshiftA32752x16x3_g3_m64", "shiftA", 32752, 16, 3, S + 119, 3, 64)
+    add("gopshiftB64x48x4_g4_m128", "shiftB", 64, 48, 4, S + 117, 4, 128)
+    # one macroblock (every non-centre candidate that clamps to (0, 0) is skipped), and two
+    add("gopP16x16x4_g4_m8", "P", 16, 16, 4, S + 120, 4, 8)
+    add("gopflat128_16x16x4_g4_m8", "flat128", 16, 16, 4, S + 120, 4, 8)
+    add("gopshiftA32x16x4_g4_m8", "shiftA", 32, 16, 4, S + 121, 4, 8)
     return out
 
 

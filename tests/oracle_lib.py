@@ -140,18 +140,35 @@ class Oracle:
         assert r >= 0, r
         return out[:r].tobytes()
 
-    def encode_gop(self, y: np.ndarray, n: int, q, gop: int, merange: int, rle=True, start_bit=0):
-        """y: (frames, h, w).  The I/P payload from start_bit: (buffer, end_bit, frame_bits)."""
+    def encode_gop(self, y: np.ndarray, n: int, q, gop: int, merange: int, rle=True, start_bit=0,
+                   stride=None, frame_pitch=None, dims=None):
+        """y: (frames, h, w), or with dims = (frames, h, w) a flat buffer whose rows lie stride
+        bytes and whose frames lie frame_pitch bytes apart.  The I/P payload from start_bit:
+        (buffer, end_bit, frame_bits)."""
         y = np.ascontiguousarray(y, dtype=np.uint8)
-        f, h, w = y.shape
+        f, h, w = y.shape if dims is None else dims
+        stride = w if stride is None else stride
+        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        assert y.size >= (f - 1) * frame_pitch + (h - 1) * stride + w
         q = np.ascontiguousarray(q, dtype=np.uint16)
         cap = (start_bit + 7) // 8 + f * (w * h * 17 // 8 + w * h // (n * n) + w * h // 32) + 64
         out = np.zeros(cap, dtype=np.uint8)
         fb = np.zeros(f, dtype=np.uint64)
-        end = self.lib.ieo_encode_gop(self._p(y), w, h, w, w * h, f, n, self._p(q, _u16p), int(rle), gop, merange,
-                                      self._p(out), out.size, start_bit, fb.ctypes.data_as(_u64p))
+        end = self.lib.ieo_encode_gop(self._p(y), w, h, stride, frame_pitch, f, n, self._p(q, _u16p), int(rle), gop,
+                                      merange, self._p(out), out.size, start_bit, fb.ctypes.data_as(_u64p))
         assert end >= 0, end
         return out, int(end), fb
+
+    def gop_vectors(self, buf: np.ndarray, frame_bits, start_bit: int, f: int, w: int, h: int, merange: int):
+        """The (vx, vy) of every macroblock of P-frame f of an encode_gop payload: the first
+        nmb * 2 * mv_bits bits after the frame's first bit (streamMVec, Block.cpp:415-423)."""
+        mv = self.bits_needed(merange)
+        nmb = (w // 16) * (h // 16)
+        p0 = start_bit + int(np.asarray(frame_bits[:f], dtype=np.uint64).sum())
+        bits = np.unpackbits(buf[p0 // 8: (p0 + nmb * 2 * mv + 7) // 8 + 1])[p0 % 8: p0 % 8 + nmb * 2 * mv]
+        v = bits.reshape(nmb * 2, mv).astype(np.int64) @ (1 << np.arange(mv - 1, -1, -1, dtype=np.int64))
+        v = np.where(v >= 1 << (mv - 1), v - (1 << mv), v)  # shift_signed (utils.hpp:265-269)
+        return [(int(a), int(b)) for a, b in v.reshape(nmb, 2)]
 
     def decode_video_gop(self, enc: bytes, n: int, motioncomp: bool = True) -> bytes:
         """A video file (any gop) decoded as the reference's VideoDecoder writes it."""
@@ -237,6 +254,24 @@ def case_expected(c) -> bytes | None:
     if "file" in c:
         return open(os.path.join(GOLDEN, c["file"]), "rb").read()
     return None
+
+
+_ENCODED = {}
+
+
+def case_encoded(c) -> bytes:
+    """A video case's reference output: the stored file or, where only its md5 is kept, the
+    oracle's encode once it has that md5 (encoded once per case)."""
+    import hashlib
+    exp = case_expected(c)
+    if exp is None:
+        exp = _ENCODED.get(c["name"])
+    if exp is None:
+        exp = load().encode_video_gop(case_input(c), c["w"], c["h"], c["n"], read_matrix(c["matrix"], c["n"]),
+                                      rle=c["rle"], gop=c["gop"], merange=c["merange"])
+        assert hashlib.md5(exp).hexdigest() == c["md5"]
+        _ENCODED[c["name"]] = exp
+    return exp
 
 
 def manifest_gop():

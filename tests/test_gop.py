@@ -48,7 +48,7 @@ DEC = [c for c in CASES if "dec1_md5" in c]
 @pytest.mark.parametrize("mc", [1, 0])
 def test_oracle_video_decode_matches_reference(c, mc):
     """The reference's VideoDecoder (Frame::loadFromStream, motion compensation on / off)."""
-    dec = O.load().decode_video_gop(O.case_expected(c), 4, bool(mc))
+    dec = O.load().decode_video_gop(O.case_encoded(c), 4, bool(mc))
     assert len(dec) == c[f"dec{mc}_size"]
     assert hashlib.md5(dec).hexdigest() == c[f"dec{mc}_md5"]
 
@@ -159,7 +159,7 @@ def test_gpu_gop_rejects_misplaced_macroblocks(codec):
 @pytest.mark.parametrize("c", DEC, ids=[c["name"] for c in DEC])
 def test_gpu_video_decode_matches_reference(codec, c):
     """P-frame video files decoded through libie_host.so -> ie_decode_gop == the reference decoder."""
-    dec, (w, h, f) = codec.decode_video_file(O.case_expected(c), 4)
+    dec, (w, h, f) = codec.decode_video_file(O.case_encoded(c), 4)
     assert (w, h) == (c["w"], c["h"])
     assert len(dec) == c["dec1_size"]
     assert hashlib.md5(dec.tobytes()).hexdigest() == c["dec1_md5"]
