@@ -11,7 +11,9 @@ OBJDIR   := build
 HIPFLAGS := --offload-arch=$(ARCH) -mcode-object-version=5 -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -ffp-contract=off \
             -Wall -Wno-unused-function
 KERNELS  := ie_encode ie_huffman ie_decode ie_pframe
-OBJS     := $(addprefix $(OBJDIR)/,$(addsuffix .o,$(KERNELS) ie_capi))
+# the C ABI's host side: every .cpp directly under csrc/ (ie_capi*.cpp, ie_tables.cpp)
+CAPI     := $(basename $(notdir $(wildcard $(CSRC)/*.cpp)))
+OBJS     := $(addprefix $(OBJDIR)/,$(addsuffix .o,$(KERNELS) $(CAPI)))
 
 .PHONY: all lib oracle ref host clean asmcheck
 all: lib host oracle
@@ -22,7 +24,7 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $(CSRC)/ie_device.h $(CSRC)/ie_common.hpp $(CSRC)/i
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(OBJDIR)/ie_capi.o: $(CSRC)/ie_capi.cpp $(CSRC)/ie_device.h include/ie_hip.h
+$(OBJDIR)/%.o: $(CSRC)/%.cpp $(CSRC)/ie_ctx.hpp $(CSRC)/ie_device.h $(CSRC)/ie_dct.h include/ie_hip.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -1,0 +1,320 @@
+// imageencoder_amd/csrc/ie_ctx.hpp -- internal to the C ABI implementation (ie_capi*.cpp,
+// ie_tables.cpp): the context, its allocators, and the checks and staging steps the entry points
+// share.  Functions that cross a file boundary are declared here, in namespace iec, and nowhere else.
+#pragma once
+#include "ie_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ie_device.h"
+
+// Profiling knobs exist only in IE_PROFILE builds (tools/variants.sh): the product library never
+// reads IE_ABLATE / IE_STAMPS / IE_DEC_STATS / IE_DEC_STAMPS, so no environment variable can change
+// its output.  IE_ABLATE_FORCE: A/B builds of an ablation.
+#ifndef IE_PROFILE
+#define IE_PROFILE 0
+#endif
+#ifndef IE_ABLATE_FORCE
+#define IE_ABLATE_FORCE 0
+#endif
+
+struct ie_pipe;  // streamed host path (ie_capi_stream.cpp)
+
+namespace iec {
+constexpr int kErrWords = 66;  // d_err: [0] look-back timeouts; sum of [2..65] = FP64 re-evaluations
+}
+
+struct ie_ctx {
+    int device = 0;
+    hipStream_t own = nullptr;
+    hipStream_t stream = nullptr;
+    std::string err;
+
+    int n = 0;
+    uint16_t q[64] = {};
+    ie::EncTables* h_tab = nullptr;
+    ie::EncTables* d_tab = nullptr;
+
+    // decoupled look-back state
+    uint64_t* d_state = nullptr;  // [kStateWordsPerTile * cap_tiles] tile chain granules (ie_common.hpp)
+    size_t cap_tiles = 0;
+    uint32_t tag = 0;
+    unsigned long long* d_ticket = nullptr;
+    unsigned long long ticket_base = 0;
+
+    uint64_t* d_frame_start = nullptr;  // [cap_frames]
+    uint64_t* d_chain_end = nullptr;    // [cap_frames]
+    size_t cap_frames = 0;
+    unsigned* d_err = nullptr;          // [kErrWords] counters that only grow
+    uint32_t* d_wave_fix = nullptr;     // [cap_tiles * waves per tile] fix-up requests of the last launch
+    int last_fix_words = 0;
+    unsigned err_seen[iec::kErrWords] = {};  // d_err's values at the previous read
+    bool use_ticket = false;            // order tiles with an atomic ticket (after a timeout)
+    hipEvent_t stage_ev[4] = {};        // timing events around the last batched histogram [0,1] / pack [2,3]
+    bool stage_rec[2] = {false, false};
+    bool stage_timing = false;          // ie_set_stage_timing
+    int fake_timeouts = 0;              // debug (IE_FAKE_TIMEOUTS): report this many look-back timeouts
+    bool fake_fired = false;            // a faked timeout was reported (the redo paths dirty the output first)
+    // Asynchronous launches (no read-back) since the last error read: a look-back timeout found
+    // at the next read is charged to them (their output is invalid), never silently retried away.
+    unsigned async_pending = 0;
+    const char* async_what = nullptr;
+
+    // staging for host-resident inputs / outputs
+    uint8_t* d_in = nullptr;
+    size_t cap_in = 0;
+    uint8_t* d_out = nullptr;
+    size_t cap_out = 0;
+    uint8_t* d_scratch = nullptr;   // quantize-only stream sink
+    size_t cap_scratch = 0;
+    int16_t* d_coef = nullptr;
+    size_t cap_coef = 0;
+
+    uint64_t last_fallbacks = 0;
+
+    // Huffman tables / histogram
+    uint32_t* d_code = nullptr;        // [256] codes, then [256/4] packed lengths (one block)
+    uint32_t* h_code = nullptr;        // pinned mirror
+    uint32_t* d_hist = nullptr;        // [256]
+    // batched Huffman: device + pinned staging (hist/first of every string, then the pack tables)
+    uint8_t* d_batch = nullptr;
+    size_t cap_batch = 0;
+    uint8_t* h_batch = nullptr;
+    size_t cap_hbatch = 0;
+    // pipelined batches: two pinned slots for the histogram read-back and two for the pack tables,
+    // each guarded by an event (no stream-wide synchronisation between batches)
+    uint8_t* h_hist[2] = {};
+    size_t cap_hhist[2] = {};
+    hipEvent_t ev_hist[2] = {};
+    int hist_count[2] = {};
+    uint8_t* h_pack[2] = {};
+    size_t cap_hpack[2] = {};
+    hipEvent_t ev_pack[2] = {};    // the table copy out of pinned slot i (on tab_stream)
+    bool pack_recorded[2] = {};
+    uint8_t* d_pack[2] = {};       // device table slots
+    size_t cap_dpack[2] = {};
+    hipEvent_t ev_packed[2] = {};  // the pack (and prefix copies) that read device slot i
+    bool packed_recorded[2] = {};
+    hipStream_t tab_stream = nullptr;
+    int pack_slot = 0;
+    int fused_count = 0;  // > 0: the last encode (ie_encode_images_counted) left this many histograms in d_chist
+    // the counted pipeline: the encoder's histograms (cleared by the first-occurrence pass that reads
+    // them: chist_zero_rows), and per pinned slot the device n / first / unresolved the rare first_full
+    // pass of ie_huffman_hist_batch_wait needs, with the batch it reads
+    uint32_t* d_chist = nullptr;
+    size_t cap_chist = 0;  // (words)
+    // leading 256-word rows of d_chist known to be zero (the counted encode skips its memset when
+    // its rows lie within them), and the rows that will be zero once the fused pass has read -- and
+    // cleared -- the last counted encode's rows
+    size_t chist_zero_rows = 0, chist_clean_after = 0;
+    bool hist_skip_zero = false;  // one shot: encode() skips its histogram memset (set by the counted encode)
+    uint8_t* d_cslot[2] = {};
+    size_t cap_cslot[2] = {};
+    bool hist_fused[2] = {};
+    const uint8_t* hist_in[2] = {};
+    size_t hist_pitch[2] = {};
+    // decoder scratch
+    uint8_t* d_dec = nullptr;          // staged stream + padding
+    size_t cap_dec = 0;
+    // 8-byte words.  Record decode: 32-bit arrays carved by dec_scratch (ie_capi_decode.cpp) -- the
+    // chunks' record bases and counts, the count workgroups' totals, the top-level entries, the
+    // speculative exits.  Huffman decode: [cap] chunk entries, [cap] symbol bases, 130 words of
+    // top-level entries.
+    uint64_t* d_walk = nullptr;
+    size_t cap_walk = 0;
+    uint32_t* d_count = nullptr;       // Huffman decode: per-chunk symbol counts, then the walk workgroups' totals
+    size_t cap_count = 0;
+    uint16_t* d_rtab = nullptr;        // chunk transfer tables and the composites of every level (record and Huffman parse)
+    size_t cap_rtab = 0;
+    uint16_t* d_rpos = nullptr;        // record parse: record positions per chunk
+    size_t cap_rpos = 0;
+    // [8].  Record decode: [1] compose tickets, [2] the speculative parse's fail flag, [3..7] walk
+    // statistics (IE_PROFILE builds).  Huffman decode: [1] the changed / invalid flag pair, [2] the
+    // symbol total, [5] its ticket.  ie_huffman_hist: [3] its ticket.
+    uint64_t* d_misc = nullptr;
+    uint64_t* h_decres = nullptr;      // record decode results, pinned host memory the device writes
+    uint64_t* d_decres = nullptr;      // directly ([0] end bit, [1] record total): no read-back copy
+    // ie_decode_images: [cap_imgres][2] the same pair per image, then [cap_imgres] the images'
+    // stream lengths on their way to d_imgbits (pinned, mapped: h_ / d_ are the two views)
+    uint64_t* h_imgres = nullptr;
+    uint64_t* d_imgres = nullptr;
+    size_t cap_imgres = 0;
+    uint64_t* d_imgbits = nullptr;     // [cap_imgbits] stream bits of every image (device)
+    size_t cap_imgbits = 0;
+    uint16_t* d_hlut = nullptr;        // Huffman decode prefix table (32768 entries)
+    size_t cap_hlut = 0;
+    uint8_t* d_hout = nullptr;         // Huffman decode output staging (host destinations)
+    size_t cap_hout = 0;
+    uint8_t* d_pix = nullptr;
+    size_t cap_pix = 0;
+    int last_chunks = 0;               // chunks of the last record decode
+    int last_groups = 0;               // and their groups
+    int last_spec = 0;                 // 1: the last record decode was the speculative parse
+    int spec_parse = 0;                // ie_set_exact_parse(ctx, 0): speculative record parse first
+    int spec_warm = 0;                 // ie_set_spec_warm(ctx, w): w warm-up chunks (<= 8)
+    unsigned long long* d_first = nullptr;  // [256]
+    ie_pipe* pipe = nullptr;           // streamed host path of image batches (created on first use)
+    // P-frame videos (ie_encode_gop): reconstructed frames (two, alternating), the prediction
+    // error's coefficients and record lengths, the scan's tile sums, the frames' bit positions
+    uint8_t* d_gop_rec = nullptr;
+    size_t cap_gop_rec = 0;
+    int16_t* d_gop_coef = nullptr;
+    size_t cap_gop_coef = 0;
+    uint32_t* d_gop_bits = nullptr;
+    size_t cap_gop_bits = 0;
+    uint64_t* d_gop_tile = nullptr;
+    size_t cap_gop_tile = 0;
+    uint64_t* d_gop_pos = nullptr;
+    size_t cap_gop_pos = 0;
+};
+
+namespace iec {
+
+inline int fail(ie_ctx* c, int code, const std::string& msg) {
+    if (c) c->err = msg;
+    return code;
+}
+
+#define HIPCHK(ctx, expr)                                                                       \
+    do {                                                                                        \
+        hipError_t e_ = (expr);                                                                 \
+        if (e_ != hipSuccess)                                                                   \
+            return iec::fail(ctx, IE_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));  \
+    } while (0)
+
+// hipMemoryTypeDevice / hipMemoryTypeHost (pinned); anything else, pageable memory included, is neither
+inline bool is_ptr_type(const void* p, hipMemoryType type) {
+    if (!p) return false;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return at.type == type;
+}
+inline bool is_device_ptr(const void* p) { return is_ptr_type(p, hipMemoryTypeDevice); }
+inline bool is_pinned_ptr(const void* p) { return is_ptr_type(p, hipMemoryTypeHost); }
+
+template <class T>
+int ensure(ie_ctx* c, T*& p, size_t& cap, size_t need_elems) {
+    if (cap >= need_elems && p) return IE_OK;
+    if (p) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipFree(p));
+        p = nullptr;
+    }
+    size_t n = std::max(need_elems, cap + cap / 2);
+    HIPCHK(c, hipMalloc(&p, n * sizeof(T)));
+    cap = n;
+    return IE_OK;
+}
+
+// pinned host staging (the stream is synchronised before an existing buffer is replaced)
+int ensure_pinned(ie_ctx* c, uint8_t*& p, size_t& cap, size_t need);
+
+// The device's view of pinned host memory (mapped, or any hipHostMalloc under unified addressing).
+template <class T>
+int device_view(ie_ctx* c, T* host, T** dev) {
+    void* dp = nullptr;
+    HIPCHK(c, hipHostGetDevicePointer(&dp, host, 0));
+    *dev = static_cast<T*>(dp);
+    return IE_OK;
+}
+
+// ---- ie_tables.cpp: a pure function of (n, q), no device involved
+bool build_tables(int n, const uint16_t* q, ie::EncTables* T);
+
+// ---- ie_capi.cpp: launch state, error counters, shared checks and staging
+int prepare_state(ie_ctx* c, int ntiles, int nframes);
+int stage_mark(ie_ctx* c, int i);
+int read_errors(ie_ctx* c, unsigned* timeouts, uint64_t* fallbacks);
+void note_async(ie_ctx* c, const char* what);
+// A look-back timeout with nothing left to re-run: IE_EDEVICE, the message with `where` appended.
+int lookback_failed(ie_ctx* c, const char* where = "");
+// After a synchronous launch's error read: no timeouts -> IE_OK, *redo = false.  Otherwise the
+// dispatch order did not hold: already ordering tiles by ticket -> IE_EDEVICE; else the context
+// switches to ticket mode and *redo = true (the caller cleans up what it must and runs again).
+int ticket_redo(ie_ctx* c, unsigned timeouts, bool* redo);
+int check_dims(ie_ctx* c, int w, int h, int nframes);
+// check_dims, then stride >= w, then (nframes > 1) frame_pitch covers a frame -- in that order
+int check_frames(ie_ctx* c, int w, int h, int nframes, size_t stride, size_t frame_pitch);
+// Host bytes (frames, or a byte string) go to d_in on the stream; device bytes are used in place.
+int stage_in(ie_ctx* c, const uint8_t* src, bool src_dev, size_t bytes, const uint8_t** dsrc);
+
+// bytes from the first pixel of the first frame to the last pixel of the last
+inline size_t frames_span(int nframes, size_t frame_pitch, size_t stride, int w, int h) {
+    return size_t(nframes - 1) * frame_pitch + stride * size_t(h - 1) + size_t(w);
+}
+inline size_t bound_bits_per_block(int n) { return 4 + 16 * size_t(n * n + 1); }
+// bits_needed of an int16 (utils.hpp:226-243): Frame::MVEC_BIT_SIZE = bits_needed(merange) (VideoBase.cpp:42)
+inline int mvec_bits(int merange) {
+    int b = 1;
+    const int16_t v = int16_t(merange);
+    while (int16_t(int16_t((v & ((1 << b) - 1)) << (16 - b)) >> (16 - b)) != v) b++;
+    return b;
+}
+
+struct Geometry {
+    int bx, by, gpr, gpf, tpf, ntiles;
+};
+inline Geometry geometry(int w, int h, int n, int nframes, int bpt = 0) {
+    Geometry g;
+    if (!bpt) bpt = ie::encode_blocks_per_thread(n);
+    g.bx = w / n;
+    g.by = h / n;
+    g.gpr = (g.bx + bpt - 1) / bpt;
+    g.gpf = g.gpr * g.by;
+    const int tpt = ie::encode_threads_per_tile();  // groups per tile
+    g.tpf = (g.gpf + tpt - 1) / tpt;
+    g.ntiles = g.tpf * nframes;
+    return g;
+}
+
+// ---- ie_capi_encode.cpp
+// One encode launch over device-resident frames (no staging, no synchronisation): the EncArgs
+// of ie_device.h, the chain state's epoch and the launch.  start_dev (optional) makes the chain
+// start at a device-resident bit position (the previous launch's chain end, ie_vstream_*);
+// chain_end (optional) receives the chain end(s) instead of the context's d_chain_end.
+struct Launch {
+    const uint8_t* dy = nullptr;
+    int w = 0, h = 0;
+    size_t stride = 0, frame_pitch = 0;
+    int nframes = 0, use_rle = 1, mode = IE_MODE_FAST;
+    uint32_t* dout = nullptr;  // word 0 = stream bytes [0, 4) (may point before the allocation)
+    size_t out_pitch = 0;      // segmented: bytes between images
+    uint64_t start_bit = 0;
+    const uint64_t* start_dev = nullptr;
+    uint64_t* chain_end = nullptr;
+    int segmented = 0;
+    int16_t* coef = nullptr;
+    uint32_t* hist = nullptr;
+    Launch(const uint8_t* dy_, int w_, int h_, size_t stride_, size_t frame_pitch_, int nframes_, int use_rle_, int mode_,
+           uint32_t* dout_, uint64_t start_bit_)
+        : dy(dy_), w(w_), h(h_), stride(stride_), frame_pitch(frame_pitch_), nframes(nframes_), use_rle(use_rle_),
+          mode(mode_), dout(dout_), start_bit(start_bit_) {}
+};
+int launch_chain(ie_ctx* c, const Launch& L);
+// Common driver of ie_encode_frames (segmented = 0) and ie_encode_images (segmented = 1).
+int encode(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,
+           int use_rle, int mode, uint8_t* out, size_t out_cap, size_t out_pitch, uint64_t start_bit,
+           int segmented, uint64_t* frame_bits, uint64_t* end_bits, int16_t* coef = nullptr,
+           uint32_t* hist = nullptr);
+
+// ---- ie_capi_stream.cpp: host frames in, host streams out
+int streamed_images(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,
+                    int use_rle, int mode, uint8_t* out, size_t out_pitch, uint64_t start_bit, uint64_t* end_bits);
+int streamed_frames(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,
+                    int use_rle, int mode, uint8_t* out, size_t out_cap, uint64_t start_bit, uint64_t* frame_bits,
+                    uint64_t* end_bit);
+void pipe_free(ie_pipe* p);
+
+}  // namespace iec

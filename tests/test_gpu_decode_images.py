@@ -91,7 +91,7 @@ def _batch(n, rle, w=64, h=48, kinds=tuple(MIXED)):
 
 
 def _planned_chunk_bits(n, span, nblocks):
-    """The chunk length the library plans for the longest span (ie_capi.cpp plan_chunks): about 24
+    """The chunk length the library plans for the longest span (ie_capi_decode.cpp plan_chunks): about 24
     (4x4) / 28 (8x8) records per chunk, a multiple of 32 within [256, 2^15]."""
     recs = 24 if n == 4 else 28
     want = max((nblocks + recs - 1) // recs, 1)
