@@ -102,6 +102,9 @@ def load_library(path: str | None = None) -> C.CDLL:
         L.ie_decode_images.restype = C.c_int
         L.ie_decode_images.argtypes = [vp, u8p, C.c_size_t, u64p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                        u8p, C.c_size_t, C.c_size_t, u64p]
+    if hasattr(L, "ie_huffman_decode_batch"):  # (absent from an older IE_LIB build under comparison)
+        L.ie_huffman_decode_batch.restype = C.c_int
+        L.ie_huffman_decode_batch.argtypes = [vp, u8p, C.c_size_t, u64p, C.c_int, u64p, u16p, u8p, C.c_size_t, u64p]
     L.ie_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(C.c_void_p)]
     L.ie_host_free.argtypes = [vp, vp]
     L.ie_vstream_open.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, u8p, C.c_uint64,
@@ -149,6 +152,10 @@ def load_host_library(path: str | None = None) -> C.CDLL:
                                        C.c_int, C.c_int, C.c_int, vp, C.c_size_t]
     H.ieh_decode_image.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, ip, ip]
     H.ieh_decode_video.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, ip, ip, ip]
+    if hasattr(H, "ieh_decode_images"):  # (absent from an older IE_LIB build under comparison)
+        H.ieh_decode_images.restype = C.c_int64
+        H.ieh_decode_images.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_uint64), C.c_int, C.c_int, vp, C.c_size_t,
+                                        ip, ip]
     H.ieh_huffman_encode.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
     H.ieh_huffman_decode.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, ip]
     H.ieh_huffman_table.argtypes = [vp, C.c_size_t, vp, C.POINTER(C.c_uint64)]
@@ -565,6 +572,32 @@ class Codec:
                                               C.byref(h)))
         return out[:r].reshape(h.value, w.value)
 
+    def decode_image_files(self, files: list[bytes], n: int) -> np.ndarray:
+        """Pixels ``(count, h, w)`` uint8 of a batch of encoded image files that share their
+        settings (ieh_decode_images): one batched Huffman decode into device slots, one batched
+        record decode that reads them in place.  Raises :class:`IEError` naming the file when one
+        is malformed or differs in its settings."""
+        H = load_host_library()
+        if not files:
+            raise IEError(IE_EINVAL, "decode_image_files: no files")
+        lens = np.array([len(f) for f in files], dtype=np.uint64)
+        pitch = max((int(lens.max()) + 15) // 16 * 16, 16)
+        src = np.zeros((len(files), pitch), dtype=np.uint8)
+        for k, f in enumerate(files):
+            src[k, : len(f)] = np.frombuffer(f, dtype=np.uint8)
+        u64p = C.POINTER(C.c_uint64)
+        w, h = C.c_int(0), C.c_int(0)
+        # size from file 0's header first: w and h come back with IE_ECAP, before any record decode
+        r = H.ieh_decode_images(self.h, src.ctypes.data, pitch, lens.ctypes.data_as(u64p), 1, n, src.ctypes.data, 0,
+                                C.byref(w), C.byref(h))
+        if r != IE_ECAP:
+            self._host_chk(r)
+        cap = len(files) * w.value * h.value
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        r = self._host_chk(H.ieh_decode_images(self.h, src.ctypes.data, pitch, lens.ctypes.data_as(u64p), len(files), n,
+                                               out.ctypes.data, cap, C.byref(w), C.byref(h)))
+        return out[:r].reshape(len(files), h.value, w.value)
+
     def decode_video_file(self, data: bytes, n: int):
         """Decoded YUV420 frames (Y + 0x80 UV fill), flat uint8, plus (w, h, frames)."""
         H = load_host_library()
@@ -654,6 +687,29 @@ class Codec:
         self._chk(self.L.ie_huffman_decode(self.h, _ptr(stream), nbytes, start_bit, _ptr(lut), _ptr(out),
                                            _nbytes(out), C.byref(n)))
         return int(n.value)
+
+    def huffman_decode_batch(self, streams, in_pitch: int, lens, start_bits, luts, out, out_pitch: int) -> np.ndarray:
+        """ie_huffman_decode_batch: ``len(lens)`` code streams in one set of launches.  Stream k is
+        ``lens[k]`` bytes at ``streams + k*in_pitch``, its code stream from bit ``start_bits[k]``,
+        its prefix table at ``luts + 32768*k`` (uint16); its symbols go to ``out + k*out_pitch``.
+        ``streams``/``luts``/``out``: numpy arrays (host) or torch tensors (device).  Returns the
+        symbol counts (uint64, one per stream); raises :class:`IEError` (``IE_EFORMAT`` /
+        ``IE_ECAP``, the message names the lowest failing image, ``e.counts`` holds the counts) --
+        the other images are decoded all the same."""
+        ln = np.ascontiguousarray(lens, dtype=np.uint64)
+        sb = np.ascontiguousarray(start_bits, dtype=np.uint64)
+        if sb.size != ln.size:
+            raise IEError(IE_EINVAL, "huffman_decode_batch: lens and start_bits differ in length")
+        nout = np.zeros(max(ln.size, 1), dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        r = self.L.ie_huffman_decode_batch(self.h, _ptr(streams), in_pitch, ln.ctypes.data_as(u64p), int(ln.size),
+                                           sb.ctypes.data_as(u64p), _ptr(luts), _ptr(out), out_pitch,
+                                           nout.ctypes.data_as(u64p))
+        if r != IE_OK:
+            e = IEError(int(r), self.L.ie_last_error(self.h).decode())
+            e.counts = nout[: ln.size]
+            raise e
+        return nout[: ln.size]
 
     def huffman_decode(self, data: bytes):
         """The Huffman decode alone (device bit walk): (decoded bytes, passthrough)."""

@@ -22,8 +22,8 @@ namespace dc {
 bool is_device(ie_ctx*, const void* p) { return ie_is_device_ptr(p) != 0; }
 
 struct Scratch {
-    DeviceBuffer enc, huf;
-    explicit Scratch(ie_ctx* c) : enc(c), huf(c) {}
+    DeviceBuffer enc, huf, pix;
+    explicit Scratch(ie_ctx* c) : enc(c), huf(c), pix(c) {}
 };
 std::mutex g_mu;
 std::map<ie_ctx*, std::unique_ptr<Scratch>> g_scratch;
@@ -270,6 +270,124 @@ static int decode_file(ie_ctx* c, const uint8_t* enc, size_t len, int n, bool vi
     return IE_OK;
 }
 
+// A batch of image files with the same settings into pixels, w*h bytes per image back to back in
+// file order (ieh_decode_images).  The decoded streams never leave the device: the dictionaries are
+// parsed on the host, ONE ie_huffman_decode_batch call decodes every coded file into device slots
+// and brings back the symbol counts with the first kHeadBytes bytes of every slot (the settings
+// headers) in its one synchronisation, and ONE ie_decode_images call reads the slots in place --
+// two synchronisations for a batch of coded files.  Files without a dictionary (the "no gain"
+// output of Huffman.cpp:329-341) form a second group that ie_decode_images reads straight from
+// the file bytes.  A group whose files are not adjacent in the batch is decoded into device
+// scratch and its images copied to their places.
+constexpr size_t kHeadBytes = 256;  // (an 8x8 header is at most 5 + 64*16 + 1 + 30 bits)
+
+static int64_t decode_files(ie_ctx* c, const uint8_t* enc, size_t enc_pitch, const uint64_t* len, int count, int n,
+                            uint8_t* out, size_t cap, int* w, int* h) {
+    auto failk = [&](int code, int k, const std::string& what) {
+        ie_set_error(c, ("file " + std::to_string(k) + ": " + what).c_str());
+        return int64_t(code);
+    };
+    const size_t K = size_t(count);
+    struct Group {
+        std::vector<int> file;        // the group's files, in file order
+        std::vector<uint64_t> start;  // coded: the code stream's first bit; else the header's
+        std::vector<uint64_t> bytes;
+    } coded, plain;
+    std::vector<int> at(K);  // a file's place in its group
+    std::vector<char> is_plain(K, 0);
+    std::vector<uint16_t> luts, lut(size_t(1) << 15);
+    for (int k = 0; k < count; k++) {
+        if (len[k] > enc_pitch) return failk(IE_EINVAL, k, "len beyond its slot of enc_pitch bytes");
+        uint64_t from = 0;
+        const int r = ie_huffman_table(enc + size_t(k) * enc_pitch, size_t(len[k]), 0, lut.data(), &from);
+        if (r < 0) return failk(r, k, "malformed Huffman dictionary");
+        Group& g = r == 1 ? plain : coded;
+        is_plain[size_t(k)] = r == 1;
+        at[size_t(k)] = int(g.file.size());
+        g.file.push_back(k);
+        g.start.push_back(from);
+        g.bytes.push_back(len[k]);
+        if (r == 0) luts.insert(luts.end(), lut.begin(), lut.end());
+    }
+    // a group's files as one pitched array: the caller's when the group is the whole batch
+    std::vector<uint8_t> gathered[2];
+    auto pitched = [&](const Group& g, std::vector<uint8_t>& buf, size_t* pitch) -> const uint8_t* {
+        if (g.file.size() == K) return (*pitch = enc_pitch, enc);
+        uint64_t longest = 0;
+        for (uint64_t b : g.bytes) longest = std::max(longest, b);
+        *pitch = std::max<size_t>((size_t(longest) + 15) / 16 * 16, 16);
+        buf.assign(*pitch * g.file.size(), 0);
+        for (size_t j = 0; j < g.file.size(); j++)
+            std::memcpy(&buf[j * *pitch], enc + size_t(g.file[j]) * enc_pitch, size_t(g.bytes[j]));
+        return buf.data();
+    };
+    Scratch& s = scratch(c);
+    int r;
+    size_t slot_pitch = 0;
+    std::vector<uint64_t> nout(coded.file.size());
+    std::vector<uint8_t> heads(coded.file.size() * kHeadBytes);
+    if (!coded.file.empty()) {
+        size_t pitch = 0;
+        const uint8_t* in = pitched(coded, gathered[0], &pitch);
+        r = algo::huffman_decode_device_batch(c, in, pitch, coded.bytes.data(), int(coded.file.size()), coded.start.data(),
+                                              luts.data(), s.huf, &slot_pitch, nout.data(), heads.data(), kHeadBytes);
+        if (r == IE_EFORMAT)
+            for (size_t j = 0; j < nout.size(); j++)
+                if (nout[j] == UINT64_MAX) return failk(r, coded.file[j], "malformed Huffman stream");
+        if (r) return r;
+    }
+    std::vector<StreamHeader> sh(K);
+    for (int k = 0; k < count; k++) {
+        const size_t j = size_t(at[size_t(k)]);
+        const bool ok = is_plain[size_t(k)]
+                            ? parse_header(enc + size_t(k) * enc_pitch, size_t(len[k]), size_t(plain.start[j]), n, false, sh[size_t(k)])
+                            : parse_header(&heads[j * kHeadBytes], size_t(std::min<uint64_t>(nout[j], kHeadBytes)), 0, n, false,
+                                           sh[size_t(k)]);
+        if (!ok) return failk(IE_EFORMAT, k, "stream shorter than its header");
+        const StreamHeader &a = sh[0], &b = sh[size_t(k)];
+        const StreamHeader& g0 = sh[size_t((is_plain[size_t(k)] ? plain : coded).file[0])];
+        if (a.q != b.q || a.rle != b.rle || a.w != b.w || a.h != b.h || g0.payload_bit != b.payload_bit)
+            return failk(IE_EINVAL, k, "settings differ from file 0's (one quant matrix, rle, width and height per batch)");
+    }
+    if (w) *w = sh[0].w;
+    if (h) *h = sh[0].h;
+    const size_t fbytes = size_t(sh[0].w) * sh[0].h;
+    if (fbytes * K > cap) return (ie_set_error(c, "pixel capacity below count * w * h"), IE_ECAP);
+    if (!fbytes) return 0;
+    if ((r = ie_set_quant(c, sh[0].q.data(), n))) return r;
+    auto decode_group = [&](const Group& g, const uint8_t* in, size_t pitch, const std::vector<uint64_t>& nbits) -> int64_t {
+        const size_t m = g.file.size();
+        const bool adjacent = size_t(g.file.back() - g.file.front()) + 1 == m;
+        int rr;
+        if (!adjacent && (rr = s.pix.reserve(m * fbytes))) return rr;
+        uint8_t* dst = adjacent ? out + size_t(g.file.front()) * fbytes : s.pix.p;
+        std::vector<uint64_t> ends(m);
+        const StreamHeader& g0 = sh[size_t(g.file[0])];
+        rr = ie_decode_images(c, in, pitch, nbits.data(), int(m), g0.payload_bit, g0.w, g0.h, g0.rle, dst, size_t(g0.w),
+                              fbytes, ends.data());
+        if (rr == IE_EFORMAT)
+            for (size_t j = 0; j < m; j++)
+                if (ends[j] == UINT64_MAX) return failk(rr, g.file[j], "stream ends before the last block");
+        if (rr) return rr;
+        for (size_t j = 0; !adjacent && j < m; j++)
+            if ((rr = ie_memcpy(c, out + size_t(g.file[j]) * fbytes, s.pix.p + j * fbytes, fbytes))) return rr;
+        return IE_OK;
+    };
+    if (!coded.file.empty()) {
+        std::vector<uint64_t> nbits(nout.size());
+        for (size_t j = 0; j < nout.size(); j++) nbits[j] = 8 * nout[j];
+        if (int64_t e = decode_group(coded, s.huf.p, slot_pitch, nbits)) return e;
+    }
+    if (!plain.file.empty()) {
+        size_t pitch = 0;
+        const uint8_t* in = pitched(plain, gathered[1], &pitch);
+        std::vector<uint64_t> nbits(plain.bytes.size());
+        for (size_t j = 0; j < nbits.size(); j++) nbits[j] = 8 * plain.bytes[j];
+        if (int64_t e = decode_group(plain, in, pitch, nbits)) return e;
+    }
+    return int64_t(fbytes * K);
+}
+
 // ----------------------------------------------------------------------------- ImageProcessor
 ImageProcessor::ImageProcessor(const std::string& src, const std::string& dst, uint16_t w, uint16_t h, bool rle,
                                QuantSpec quant)
@@ -495,6 +613,14 @@ int64_t ieh_decode_image(ie_ctx* c, const uint8_t* enc, size_t len, int n, uint8
     if (r) return r;
     std::memcpy(out, pix.data(), pix.size());
     return int64_t(pix.size());
+}
+
+int64_t ieh_decode_images(ie_ctx* c, const uint8_t* enc, size_t enc_pitch, const uint64_t* len, int count, int n,
+                          uint8_t* out, size_t cap, int* w, int* h) {
+    if (!c) return IE_EINVAL;
+    if (!enc || !len || !out || count < 1 || (n != 4 && n != 8))
+        return (ie_set_error(c, "ieh_decode_images: null argument, count < 1 or a block size other than 4 or 8"), IE_EINVAL);
+    return dc::decode_files(c, enc, enc_pitch, len, count, n, out, cap, w, h);
 }
 
 int64_t ieh_decode_video(ie_ctx* c, const uint8_t* enc, size_t len, int n, uint8_t* out, size_t cap, int* w, int* h,

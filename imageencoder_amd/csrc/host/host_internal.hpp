@@ -53,6 +53,9 @@ int huffman_device_batch(ie_ctx* c, const uint8_t* din, size_t in_pitch, const u
                          size_t out_pitch, int64_t* bytes, std::string& err, const uint64_t* d_end_bits = nullptr);
 int huffman_device_batch_finish(ie_ctx* c, const uint8_t* din, size_t in_pitch, int count, int slot, uint8_t* dout,
                                 size_t out_pitch, int64_t* bytes, std::string& err);
+int huffman_decode_device_batch(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64_t* len, int count,
+                                const uint64_t* start, const uint16_t* luts, dc::DeviceBuffer& out, size_t* out_pitch,
+                                uint64_t* nout, uint8_t* heads, size_t head_bytes);
 }  // namespace algo
 
 namespace dc {

@@ -352,4 +352,22 @@ int Huffman::decode(ie_ctx* ctx, const uint8_t* in, size_t n, std::vector<uint8_
     return IE_OK;
 }
 
+// A batch of Huffman-coded streams (host memory: stream k is len[k] bytes at in + k*in_pitch, its
+// code stream from bit start[k], its prefix table at luts + 32768*k) decoded by ONE
+// ie_huffman_decode_batch call into device slots of `out`: 16-byte aligned, *out_pitch a multiple
+// of 16, so that ie_decode_images reads them in place.  A slot holds 8*len + 16 symbols of the
+// longest stream (a code is at least one bit long).  heads receives the first head_bytes bytes of
+// every slot in the same synchronisation; nout[k] = UINT64_MAX for a stream no code sequence spells.
+int huffman_decode_device_batch(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64_t* len, int count,
+                                const uint64_t* start, const uint16_t* luts, dc::DeviceBuffer& out, size_t* out_pitch,
+                                uint64_t* nout, uint8_t* heads, size_t head_bytes) {
+    uint64_t longest = 0;
+    for (int k = 0; k < count; k++) longest = std::max(longest, len[k]);
+    const size_t pitch = std::max((size_t(longest) * 8 + 16 + 15) / 16 * 16, (head_bytes + 15) / 16 * 16);
+    int r;
+    if ((r = out.reserve(pitch * size_t(count)))) return r;
+    *out_pitch = pitch;
+    return ie_huffman_decode_batch_heads(c, in, in_pitch, len, count, start, luts, out.p, pitch, nout, heads, head_bytes);
+}
+
 }  // namespace algo

@@ -93,6 +93,177 @@ int hist_out(ie_ctx* c, uint32_t* hist, uint64_t* first_pos, const void* dh, con
     return IE_OK;
 }
 
+// Walk chunk of the Huffman decode; IE_HUF_CHUNK overrides (tuning aid).  1024 bits measured
+// best on a 4K payload (tools/gpu_huf_chunk.sh: 0.30-0.32 ms against 0.34 at 512, 0.37 at 768
+// and 2048, 0.55 at 4096)
+uint64_t huf_chunk_bits() {
+    static const uint64_t huf_chunk = getenv("IE_HUF_CHUNK") ? strtoull(getenv("IE_HUF_CHUNK"), nullptr, 10) : 1024;
+    // (at most 2048: the per-chunk symbol counts and middle offsets are u16, and huf_emit_kernel's
+    // LDS grows ~33 bytes per chunk bit -- 4096-bit chunks would not fit gfx950's 160 KB)
+    return std::min<uint64_t>(2048, std::max<uint64_t>(256, huf_chunk));
+}
+
+constexpr size_t kHufBatchBytes = size_t(1) << 30;  // ie_huffman_decode_batch: scratch of one sub-batch
+
+// Scratch of the batched decode under a chunk plan: per image its table entries, chunk entries and
+// symbol bases (8-byte words), symbol counts, count-workgroup totals and top-level entries
+// (32-bit words); for `batch` images one array per kind, every image's part in turn.
+struct HufScratch {
+    size_t tab, wg, E, img_bytes;
+    size_t base_at, tab_at, count_at, wg_at, e_at, bytes;  // byte offsets for `batch` images
+};
+HufScratch huf_scratch(size_t nch, size_t batch) {
+    HufScratch s;
+    s.tab = ie::huffman_batch_tab(int(nch));
+    s.wg = ie::huffman_batch_wg(int(nch));
+    s.E = ie::huffman_batch_entries();
+    s.img_bytes = s.tab * 2 + nch * 16 + (nch + s.wg + s.E) * 4;
+    s.base_at = batch * nch * 8;
+    s.tab_at = (s.base_at + batch * nch * 8 + 15) / 16 * 16;  // (s.tab is a multiple of 8 entries)
+    s.count_at = s.tab_at + batch * s.tab * 2;
+    s.wg_at = s.count_at + batch * nch * 4;
+    s.e_at = s.wg_at + batch * s.wg * 4;
+    s.bytes = s.e_at + batch * s.E * 4;
+    return s;
+}
+
+// ie_huffman_decode_batch, plus (heads, optional, host) the first head_bytes <= out_pitch bytes
+// of every output slot in the same synchronisation: heads + k*head_bytes (the bytes past image
+// k's symbols are whatever the slot held).
+int huffman_decode_batch(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64_t* len, int count,
+                         const uint64_t* start_bit, const uint16_t* lut, uint8_t* out, size_t out_pitch, uint64_t* nout,
+                         uint8_t* heads, size_t head_bytes) {
+    if (!c) return IE_EINVAL;
+    if (!in || !len || !start_bit || !lut || !nout || (!out && out_pitch)) return fail(c, IE_EINVAL, "null argument");
+    if (count < 1) return fail(c, IE_EINVAL, "count must be at least 1");
+    if (heads && head_bytes > out_pitch) return fail(c, IE_EINVAL, "head_bytes beyond out_pitch");
+    const size_t K = size_t(count);
+    uint64_t max_span = 0, max_len = 0;
+    for (size_t k = 0; k < K; k++) {
+        nout[k] = 0;
+        if (len[k] > in_pitch)
+            return fail(c, IE_EINVAL, "image " + std::to_string(k) + ": len beyond its slot of in_pitch bytes");
+        if (start_bit[k] > len[k] * 8) return fail(c, IE_EINVAL, "image " + std::to_string(k) + ": start_bit beyond the stream");
+        max_span = std::max(max_span, len[k] * 8 - start_bit[k]);
+        max_len = std::max(max_len, len[k]);
+    }
+    const uint64_t chunk_bits = huf_chunk_bits();
+    const uint64_t nch64 = (max_span + chunk_bits - 1) / chunk_bits;
+    if (!nch64) return IE_OK;  // every code stream is empty
+    if (nch64 > uint64_t(INT32_MAX)) return fail(c, IE_EINVAL, "stream too long for one decode call");
+    const size_t nch = size_t(nch64);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r;
+    // the kernels read a stream only through their LDS staging, which stops at its last byte:
+    // 4-byte-aligned, 4-byte-pitched device streams are read in place, and device tables too
+    const bool in_dev = is_device_ptr(in);
+    const uint8_t* src = in;
+    size_t pitch = in_pitch;
+    if (!in_dev || (reinterpret_cast<uintptr_t>(in) & 3u) || (in_pitch & 3u)) {
+        pitch = (size_t(max_len) + 3) / 4 * 4 + 16;
+        if ((r = ensure(c, c->d_dec, c->cap_dec, pitch * K))) return r;
+        if (in_dev) {
+            HIPCHK(c, hipMemcpy2DAsync(c->d_dec, pitch, in, in_pitch, size_t(max_len), K, hipMemcpyDeviceToDevice, c->stream));
+        } else {
+            for (size_t k = 0; k < K; k++)
+                if (len[k])
+                    HIPCHK(c, hipMemcpyAsync(c->d_dec + k * pitch, in + k * in_pitch, size_t(len[k]), hipMemcpyHostToDevice,
+                                             c->stream));
+        }
+        src = c->d_dec;
+    }
+    const uint16_t* dlut = lut;
+    if (!is_device_ptr(lut) || reinterpret_cast<uintptr_t>(lut) % 2) {
+        if ((r = ensure(c, c->d_hlut, c->cap_hlut, K * 32768))) return r;
+        HIPCHK(c, hipMemcpyAsync(c->d_hlut, lut, K * 32768 * sizeof(uint16_t),
+                                 is_device_ptr(lut) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+        dlut = c->d_hlut;
+    }
+    const bool out_dev = is_device_ptr(out);
+    uint8_t* dout = out;
+    if (!out_dev) {
+        if ((r = ensure(c, c->d_hout, c->cap_hout, K * out_pitch + 1))) return r;
+        dout = c->d_hout;
+    }
+    // the lengths and first bits up, the flag pairs and totals cleared
+    if ((r = ensure(c, c->d_hufb_res, c->cap_hufb_res, 4 * K))) return r;
+    if ((r = ensure_pinned(c, c->h_hufb_res, c->cap_hhufb_res, 4 * K * sizeof(uint64_t) + K * head_bytes))) return r;
+    uint64_t* hres = reinterpret_cast<uint64_t*>(c->h_hufb_res);
+    uint8_t* hheads = c->h_hufb_res + 4 * K * sizeof(uint64_t);
+    for (size_t k = 0; k < K; k++) {
+        hres[k] = len[k] * 8;
+        hres[K + k] = start_bit[k];
+    }
+    uint64_t* dres = c->d_hufb_res;
+    HIPCHK(c, hipMemcpyAsync(dres, hres, 2 * K * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(dres + 2 * K, 0, 2 * K * sizeof(uint64_t), c->stream));
+    // per-image scratch; a batch whose scratch would pass kHufBatchBytes runs as sub-batches one
+    // after another on the stream (IE_DEC_BATCH_MAX, read on every call, lowers their size further)
+    size_t batch = std::max<size_t>(1, kHufBatchBytes / huf_scratch(nch, 1).img_bytes);
+    if (const char* eb = getenv("IE_DEC_BATCH_MAX"))
+        if (atoi(eb) > 0) batch = std::min<size_t>(batch, size_t(atoi(eb)));
+    batch = std::min(batch, K);
+    const HufScratch hs = huf_scratch(nch, batch);
+    if ((r = ensure(c, c->d_hufb, c->cap_hufb, hs.bytes))) return r;
+    ie::HufBatch b{};
+    b.nchunks = int(nch);
+    b.chunk_bits = chunk_bits;
+    b.img_words = pitch / 4;
+    b.entry = reinterpret_cast<uint64_t*>(c->d_hufb);
+    b.base = reinterpret_cast<uint64_t*>(c->d_hufb + hs.base_at);
+    b.tab = reinterpret_cast<uint16_t*>(c->d_hufb + hs.tab_at);
+    b.count = reinterpret_cast<uint32_t*>(c->d_hufb + hs.count_at);
+    b.wgsum = reinterpret_cast<uint32_t*>(c->d_hufb + hs.wg_at);
+    b.E = reinterpret_cast<uint32_t*>(c->d_hufb + hs.e_at);
+    b.out_pitch = out_pitch;
+    for (size_t k0 = 0; k0 < K; k0 += batch) {  // (sub-batches share the scratch: stream order)
+        b.images = int(std::min(batch, K - k0));
+        b.words = reinterpret_cast<const uint32_t*>(src + k0 * pitch);
+        b.nbits = dres + k0;
+        b.start_bit = dres + K + k0;
+        b.lut = dlut + k0 * 32768;
+        b.flags = reinterpret_cast<unsigned*>(dres + 2 * K + k0);
+        b.total = dres + 3 * K + k0;
+        b.out = dout + k0 * out_pitch;
+        if (ie::huffman_decode_images(b, false, c->stream) < 0) return fail(c, IE_EHIP, "Huffman decode walk failed");
+        HIPCHK(c, hipGetLastError());
+        // the emit follows at once, bounded by out_pitch (a symbol past it is not written and flags
+        // its image): no wait for the totals
+        ie::huffman_decode_images(b, true, c->stream);
+        HIPCHK(c, hipGetLastError());
+    }
+    // every flag pair and total in ONE read, and the call's one synchronisation
+    HIPCHK(c, hipMemcpyAsync(hres + 2 * K, dres + 2 * K, 2 * K * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (heads && head_bytes)
+        HIPCHK(c, hipMemcpy2DAsync(hheads, head_bytes, dout, out_pitch, head_bytes, K, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (heads && head_bytes) std::memcpy(heads, hheads, K * head_bytes);
+    int code = IE_OK;
+    size_t bad = 0;
+    bool copied = false;
+    for (size_t k = K; k-- > 0;) {
+        const uint64_t total = hres[3 * K + k];
+        const bool invalid = uint32_t(hres[2 * K + k] >> 32) != 0;
+        nout[k] = invalid ? UINT64_MAX : total;
+        if (invalid || total > out_pitch) {
+            code = invalid ? IE_EFORMAT : IE_ECAP;
+            bad = k;
+        }
+        // a host destination: the symbols of every decodable image, its slot's other bytes untouched
+        const size_t nb = size_t(std::min<uint64_t>(total, out_pitch));
+        if (!out_dev && !invalid && nb) {
+            HIPCHK(c, hipMemcpyAsync(out + k * out_pitch, dout + k * out_pitch, nb, hipMemcpyDeviceToHost, c->stream));
+            copied = true;
+        }
+    }
+    if (copied) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (code == IE_EFORMAT)
+        return fail(c, code, "image " + std::to_string(bad) + ": Huffman stream holds a bit string no code prefixes");
+    if (code == IE_ECAP)
+        return fail(c, code, "image " + std::to_string(bad) + ": output capacity below the decoded symbol count");
+    return IE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -523,13 +694,7 @@ int ie_huffman_decode(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_b
         dlut = c->d_hlut;
     }
     const uint64_t nbits = uint64_t(len) * 8;
-    // walk chunk of the Huffman decode; IE_HUF_CHUNK overrides (tuning aid).  1024 bits measured
-    // best on a 4K payload (tools/gpu_huf_chunk.sh: 0.30-0.32 ms against 0.34 at 512, 0.37 at 768
-    // and 2048, 0.55 at 4096)
-    static const uint64_t huf_chunk = getenv("IE_HUF_CHUNK") ? strtoull(getenv("IE_HUF_CHUNK"), nullptr, 10) : 1024;
-    // (at most 2048: the per-chunk symbol counts and middle offsets are u16, and huf_emit_kernel's
-    // LDS grows ~33 bytes per chunk bit -- 4096-bit chunks would not fit gfx950's 160 KB)
-    const uint64_t chunk_bits = std::min<uint64_t>(2048, std::max<uint64_t>(256, huf_chunk));
+    const uint64_t chunk_bits = huf_chunk_bits();
     const size_t nchunks = size_t((nbits - start_bit + chunk_bits - 1) / chunk_bits);
     if (!nchunks) return IE_OK;
     // d_walk: [cap] entries, [cap] symbol bases, then 128 words of top-level entries (256 x u32)
@@ -580,6 +745,18 @@ int ie_huffman_decode(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_b
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (f[1]) return fail(c, IE_EFORMAT, "Huffman stream holds a bit string no code prefixes");
     return IE_OK;
+}
+
+int ie_huffman_decode_batch(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64_t* len, int count,
+                            const uint64_t* start_bit, const uint16_t* lut, uint8_t* out, size_t out_pitch, uint64_t* nout) {
+    return huffman_decode_batch(c, in, in_pitch, len, count, start_bit, lut, out, out_pitch, nout, nullptr, 0);
+}
+
+int ie_huffman_decode_batch_heads(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64_t* len, int count,
+                                  const uint64_t* start_bit, const uint16_t* lut, uint8_t* out, size_t out_pitch,
+                                  uint64_t* nout, uint8_t* heads, size_t head_bytes) {
+    if (!heads) return c ? fail(c, IE_EINVAL, "null argument") : IE_EINVAL;
+    return huffman_decode_batch(c, in, in_pitch, len, count, start_bit, lut, out, out_pitch, nout, heads, head_bytes);
 }
 
 }  // extern "C"

@@ -154,6 +154,17 @@ struct ie_ctx {
     size_t cap_hlut = 0;
     uint8_t* d_hout = nullptr;         // Huffman decode output staging (host destinations)
     size_t cap_hout = 0;
+    // ie_huffman_decode_batch.  d_hufb: the scratch of one sub-batch, per image and sized from the
+    // longest stream, one array per kind holding every image's part in turn (HufScratch,
+    // ie_capi_huffman.cpp).  d_hufb_res, 8-byte words for the whole batch: [n] stream bits, [n] first
+    // code bits, [n] flag pairs (capacity, invalid code), [n] symbol totals; h_hufb_res: its pinned
+    // mirror (the first two arrays go up, the last two come back in the call's one read).
+    uint8_t* d_hufb = nullptr;
+    size_t cap_hufb = 0;
+    uint64_t* d_hufb_res = nullptr;
+    size_t cap_hufb_res = 0;
+    uint8_t* h_hufb_res = nullptr;
+    size_t cap_hhufb_res = 0;
     uint8_t* d_pix = nullptr;
     size_t cap_pix = 0;
     int last_chunks = 0;               // chunks of the last record decode

@@ -74,7 +74,37 @@ struct HufArgs {
     int levels;
     const uint32_t* E;
     uint64_t out_cap;   // bytes of out (the emit launched before the total is known checks it)
+    // image batch (the kernels' B instantiations; huf_image): the strides between the images' parts
+    size_t img_words;           // stream words
+    const uint64_t* img_nbits;  // [images] stream bits
+    const uint64_t* img_start;  // [images] first bit of the code stream
+    size_t img_tab;             // table entries (tables, composites, counts, middles)
+    uint32_t img_chunks, img_wg, img_E;
+    size_t out_pitch;           // bytes between the images' output slots (out_cap: bytes of a slot)
 };
+
+// Image batch: the launch's arguments rebased to image blockIdx.y -- its stream, its length, its
+// first bit (the dictionaries differ in length, so every image's chunk grid has its own phase),
+// its prefix table, its scratch, its flag pair and its output slot -- so that every pass below runs
+// on it as on a single stream.  One chunk plan serves the batch (nchunks from the longest stream):
+// a chunk past its image's stream holds no code.  (lvl[] is left alone: see huf_count_kernel.)
+template <bool B>
+__device__ __forceinline__ void huf_image(HufArgs& a) {
+    if constexpr (B) {
+        const size_t y = blockIdx.y;
+        a.words += y * a.img_words;
+        a.nbits = a.img_nbits[y];
+        a.start_bit = a.img_start[y];
+        a.lut += y << 15;
+        a.entry += y * a.img_chunks;
+        a.count += y * a.img_chunks;
+        a.base += y * a.img_chunks;
+        a.wgsum += y * a.img_wg;
+        a.changed += 2 * y;
+        a.E += y * a.img_E;
+        a.out += y * a.out_pitch;
+    }
+}
 
 __device__ __forceinline__ void huf_l1(const uint16_t* lut, uint16_t* l1) {
     constexpr int B = 8;  // loads in flight per thread
@@ -107,8 +137,15 @@ __device__ __forceinline__ uint64_t huf_wg_prefix(const uint32_t* wgsum, int g, 
 }
 
 // total receives the symbol count (device, 1 word): the sum of the walk's workgroup totals.
-__global__ __launch_bounds__(kTPB) void huf_total_kernel(const uint32_t* wgsum, int nwg, uint64_t* total) {
+// B (image batch): blockIdx.y = the image, its totals img_wg words after the previous image's.
+template <bool B = false>
+__global__ __launch_bounds__(kTPB) void huf_total_kernel(const uint32_t* wgsum, int nwg, uint64_t* total,
+                                                         uint32_t img_wg) {
     __shared__ alignas(8) uint32_t scratch[8];
+    if constexpr (B) {
+        wgsum += size_t(blockIdx.y) * img_wg;
+        total += blockIdx.y;
+    }
     const uint64_t t = huf_wg_prefix(wgsum, nwg, scratch);
     if (threadIdx.x == 0) *total = t;
 }
@@ -1109,6 +1146,11 @@ constexpr uint32_t kHufSync = IE_HUF_SYNC;
 #define IE_HUF_TC 64
 #endif
 constexpr int kHufTC = IE_HUF_TC;  // chunks per table workgroup: its survivors fill a wave
+// B (image batch): blockIdx.y = the image (huf_image), its table arrays img_tab entries after the
+// previous image's.  A workgroup whose chunks all lie past its image's stream walks nothing and
+// writes the rows those walks would end in: every entry leaves at the next chunk's first bit with
+// no code counted, the middle boundary at the chunk's end.
+template <bool B = false>
 __global__ __launch_bounds__(kTPB) void huf_table_kernel(HufArgs a, uint16_t* tab, uint16_t* cnt, uint16_t* mo,
                                                           uint16_t* mc) {
     constexpr int S = kHufTC * 16, U = S / kTPB;  // walk slots (chunk, entry); slots per thread
@@ -1120,11 +1162,31 @@ __global__ __launch_bounds__(kTPB) void huf_table_kernel(HufArgs a, uint16_t* ta
     __shared__ uint16_t KM[S];                 // its codes from P to that boundary
     extern __shared__ uint32_t L[];            // the workgroup's chunks' bits (+ 64 past the last)
     const int tid = threadIdx.x;
+    huf_image<B>(a);
+    if constexpr (B) {
+        const size_t img = size_t(blockIdx.y) * a.img_tab;
+        tab += img;
+        cnt += img;
+        mo += img;
+        mc += img;
+    }
     if (tid == 0) R[S] = 0u;
     const int k0 = blockIdx.x * kHufTC;
     const uint32_t C = uint32_t(a.chunk_bits);
     const int m = min(kHufTC, a.nchunks - k0);
     const uint64_t c0 = a.start_bit + uint64_t(k0) * C;
+    if constexpr (B) {
+        if (c0 >= a.nbits) {
+            for (int i = tid; i < m * kHufD; i += kTPB) {
+                const size_t r = size_t(k0) * kHufD + i;
+                tab[r] = 0;
+                cnt[r] = 0;
+                mo[r] = uint16_t(C);
+                mc[r] = 0;
+            }
+            return;
+        }
+    }
     const uint64_t base = c0 & ~31ull;
     const uint32_t s0 = uint32_t(c0 - base);
     stage_words_pad(L, a.words, base >> 5, int((s0 + uint32_t(m) * C + 64) >> 5) + 2, a.nbits, tid, kTPB);
@@ -1226,8 +1288,13 @@ __global__ __launch_bounds__(kTPB) void huf_table_kernel(HufArgs a, uint16_t* ta
 
 // The true entry of every chunk through the composed tables, its symbol count from the table pass,
 // and the workgroup scan of the counts (base[k], wgsum[g]) -- no walk.
+// B (image batch): blockIdx.y = the image; lvl[] stays image 0's -- this image's arrays lie img_tab
+// entries after -- and is indexed by constants only, as in rec_chunk_entry.  A chunk past its
+// image's stream counts nothing (its table rows say so).
+template <bool B = false>
 __global__ __launch_bounds__(kTPB) void huf_count_kernel(HufArgs a, const uint16_t* cnt) {
     __shared__ alignas(8) uint32_t scratch[8];
+    huf_image<B>(a);
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t c = 0;
     if (k < a.nchunks) {
@@ -1235,10 +1302,24 @@ __global__ __launch_bounds__(kTPB) void huf_count_kernel(HufArgs a, const uint16
         int u = k;
         for (int l = 0; l < a.levels; l++) u /= kHufG;
         uint32_t x = a.E[u];
-        for (int l = a.levels - 1; l >= 0; l--) {
-            int ul = k;
-            for (int m = 0; m < l; m++) ul /= kHufG;
-            x = a.lvl[l][size_t(ul) * kHufD + x];
+        if constexpr (B) {
+            const size_t img = size_t(blockIdx.y) * a.img_tab;
+            cnt += img;
+#pragma unroll
+            for (int l = kRecMaxLevels - 1; l >= 0; l--) {
+                if (l < a.levels) {
+                    int ul = k;
+#pragma unroll
+                    for (int m = 0; m < l; m++) ul /= kHufG;
+                    x = a.lvl[l][img + size_t(ul) * kHufD + x];
+                }
+            }
+        } else {
+            for (int l = a.levels - 1; l >= 0; l--) {
+                int ul = k;
+                for (int m = 0; m < l; m++) ul /= kHufG;
+                x = a.lvl[l][size_t(ul) * kHufD + x];
+            }
         }
         a.entry[k] = cstart + x;
         c = cnt[size_t(k) * kHufD + x];
@@ -1262,15 +1343,28 @@ __global__ __launch_bounds__(kTPB) void huf_count_kernel(HufArgs a, const uint16
 #endif
 constexpr int kHufEmitT = 2 * kTPB;  // emit threads: two per chunk (its halves, split at the
                                      // middle boundary the table pass recorded)
+// B (image batch): blockIdx.y = the image (huf_image), writing into its own slot of out_cap bytes;
+// a workgroup whose chunks all lie past its image's stream has nothing to write.  (The same LDS
+// as the single-stream form: the batch adds none.)
+template <bool B = false>
 __global__ __launch_bounds__(kHufEmitT) void huf_emit_kernel(HufArgs a, const uint16_t* mo, const uint16_t* mc) {
     __shared__ uint16_t l1[1 << kHufL1];
     __shared__ alignas(8) uint64_t scratch[kHufEmitT / 64];
     __shared__ uint8_t sym[IE_HUF_EMIT_LDS > 0 ? IE_HUF_EMIT_LDS : 1];
     extern __shared__ uint32_t L[];  // the workgroup's chunks' bits (+ 64 past the last)
     const int tid = threadIdx.x, j = tid % kTPB, half = tid / kTPB;
+    huf_image<B>(a);
+    if constexpr (B) {
+        const size_t img = size_t(blockIdx.y) * a.img_tab;
+        mo += img;
+        mc += img;
+    }
     const uint32_t C = uint32_t(a.chunk_bits);
     const int k0 = blockIdx.x * kTPB, m = min(kTPB, a.nchunks - k0);
     const uint64_t c0 = a.start_bit + uint64_t(k0) * C;
+    if constexpr (B) {
+        if (c0 >= a.nbits) return;
+    }
     const uint64_t base = c0 & ~31ull;
     const uint32_t s0 = uint32_t(c0 - base);
     stage_words_pad(L, a.words, base >> 5, int((s0 + uint32_t(m) * C + 64) >> 5) + 2, a.nbits, tid, kHufEmitT);
@@ -1320,6 +1414,36 @@ __global__ __launch_bounds__(kHufEmitT) void huf_emit_kernel(HufArgs a, const ui
     for (uint32_t i = tid; i < tot && pre + i < a.out_cap; i += kHufEmitT) a.out[pre + i] = sym[i];
 }
 
+// The launches of one decode over a.nchunks chunks (write = false: table pass, composition, counts
+// and total; write = true: the emit), for one stream or (B) for `images` streams side by side.
+template <bool B>
+static int huf_launch(HufArgs a, uint16_t* tab, uint32_t* E, unsigned* ticket, uint64_t* total, bool write, int images,
+                      hipStream_t s) {
+    const int nchunks = a.nchunks;
+    const uint64_t chunk_bits = a.chunk_bits;
+    const dim3 g((nchunks + kTPB - 1) / kTPB, images), blk(kTPB);
+    if (write) {
+        const uint16_t* cnt = tab + compose_rows<kHufD, kHufG>(nchunks) * kHufD;
+        const uint16_t* mo = cnt + size_t(nchunks) * kHufD;
+        hipLaunchKernelGGL(huf_emit_kernel<B>, g, dim3(kHufEmitT), size_t(pad_words(int(((uint64_t(kTPB) * chunk_bits + 95) >> 5) + 3))) * 4, s,
+                           a, mo, mo + size_t(nchunks) * kHufD);
+        return 0;
+    }
+    const size_t lds = size_t(pad_words(int(((uint64_t(kHufTC) * chunk_bits + 95) >> 5) + 3))) * 4;
+    // the symbol counts after the composition's rows (compose_kernel rewrites the exit tables)
+    uint16_t* cnt = tab + compose_rows<kHufD, kHufG>(nchunks) * kHufD;
+    uint16_t* mo = cnt + size_t(nchunks) * kHufD;  // then the middle boundaries and their counts
+    hipLaunchKernelGGL(huf_table_kernel<B>, dim3((nchunks + kHufTC - 1) / kHufTC, images), blk, lds, s, a, tab, cnt, mo,
+                       mo + size_t(nchunks) * kHufD);
+    const int levels = launch_compose<kHufD, kHufG, B>(tab, nchunks, E, ticket, a.lvl, s, images, a.img_tab, a.img_E);
+    if (levels < 0) return -1;
+    a.levels = levels;
+    a.E = E;
+    hipLaunchKernelGGL(huf_count_kernel<B>, g, blk, 0, s, a, cnt);
+    hipLaunchKernelGGL(huf_total_kernel<B>, dim3(1, images), blk, 0, s, a.wgsum, int(g.x), total, a.img_wg);
+    return levels;
+}
+
 int huffman_decode_device(const uint32_t* W, uint64_t nbits, uint64_t start_bit, const uint16_t* lut,
                           uint64_t chunk_bits, uint64_t* entry, uint16_t* tab, uint32_t* E, unsigned* ticket,
                           uint32_t* count, uint64_t* base, unsigned* changed, uint64_t* total, uint8_t* out,
@@ -1341,27 +1465,38 @@ int huffman_decode_device(const uint32_t* W, uint64_t nbits, uint64_t start_bit,
     a.base = base;
     a.out = out;
     a.out_cap = out_cap;
-    const dim3 g((nchunks + kTPB - 1) / kTPB), blk(kTPB);
-    if (write) {
-        const uint16_t* cnt = tab + compose_rows<kHufD, kHufG>(nchunks) * kHufD;
-        const uint16_t* mo = cnt + size_t(nchunks) * kHufD;
-        hipLaunchKernelGGL(huf_emit_kernel, g, dim3(kHufEmitT), size_t(pad_words(int(((uint64_t(kTPB) * chunk_bits + 95) >> 5) + 3))) * 4, s,
-                           a, mo, mo + size_t(nchunks) * kHufD);
-        return 0;
-    }
-    const size_t lds = size_t(pad_words(int(((uint64_t(kHufTC) * chunk_bits + 95) >> 5) + 3))) * 4;
-    // the symbol counts after the composition's rows (compose_kernel rewrites the exit tables)
-    uint16_t* cnt = tab + compose_rows<kHufD, kHufG>(nchunks) * kHufD;
-    uint16_t* mo = cnt + size_t(nchunks) * kHufD;  // then the middle boundaries and their counts
-    hipLaunchKernelGGL(huf_table_kernel, dim3((nchunks + kHufTC - 1) / kHufTC), blk, lds, s, a, tab, cnt, mo,
-                       mo + size_t(nchunks) * kHufD);
-    const int levels = launch_compose<kHufD, kHufG>(tab, nchunks, E, ticket, a.lvl, s);
-    if (levels < 0) return -1;
-    a.levels = levels;
-    a.E = E;
-    hipLaunchKernelGGL(huf_count_kernel, g, blk, 0, s, a, cnt);
-    hipLaunchKernelGGL(huf_total_kernel, dim3(1), blk, 0, s, a.wgsum, int(g.x), total);
-    return levels;
+    return huf_launch<false>(a, tab, E, ticket, total, write, 1, s);
+}
+
+size_t huffman_batch_tab(int nchunks) {
+    return ((compose_rows<kHufD, kHufG>(nchunks) + 3 * size_t(nchunks)) * kHufD + 7) / 8 * 8;
+}
+uint32_t huffman_batch_wg(int nchunks) { return uint32_t((nchunks + kTPB - 1) / kTPB); }
+uint32_t huffman_batch_entries() { return uint32_t(kHufG); }
+
+int huffman_decode_images(const HufBatch& b, bool write, hipStream_t s) {
+    if (b.nchunks <= 0 || b.images <= 0) return 0;
+    HufArgs a{};
+    a.words = b.words;
+    a.chunk_bits = b.chunk_bits;
+    a.nchunks = b.nchunks;
+    a.lut = b.lut;
+    a.entry = b.entry;
+    a.count = b.count;
+    a.wgsum = b.wgsum;
+    a.changed = b.flags;
+    a.base = b.base;
+    a.out = b.out;
+    a.out_cap = b.out_pitch;
+    a.img_words = b.img_words;
+    a.img_nbits = b.nbits;
+    a.img_start = b.start_bit;
+    a.img_tab = huffman_batch_tab(b.nchunks);
+    a.img_chunks = uint32_t(b.nchunks);
+    a.img_wg = huffman_batch_wg(b.nchunks);
+    a.img_E = uint32_t(kHufG);
+    a.out_pitch = b.out_pitch;
+    return huf_launch<true>(a, b.tab, b.E, nullptr, b.total, write, b.images, s);
 }
 
 size_t huffman_table_rows(uint64_t nbits, uint64_t start_bit, uint64_t chunk_bits) {

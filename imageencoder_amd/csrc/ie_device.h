@@ -284,6 +284,37 @@ int huffman_decode_device(const uint32_t* W, uint64_t nbits, uint64_t start_bit,
                           bool write, hipStream_t s, uint64_t out_cap = ~0ull);
 size_t huffman_table_rows(uint64_t nbits, uint64_t start_bit, uint64_t chunk_bits);
 
+// The same decode for `images` streams side by side in one set of launches (the kernels' batch
+// instantiations: blockIdx.y = the image).  One chunk plan: nchunks chunks of chunk_bits for every
+// image, from the longest code stream; an image's chunks past its stream hold no code.  Every
+// array holds the images' parts one after another: image k's at k times the stride given.
+struct HufBatch {
+    int images, nchunks;
+    uint64_t chunk_bits;
+    const uint32_t* words;      // image k's stream: words + k * img_words
+    size_t img_words;
+    const uint64_t* nbits;      // [images] (device) stream bits
+    const uint64_t* start_bit;  // [images] (device) first bit of the code stream
+    const uint16_t* lut;        // [images][32768] prefix tables
+    uint16_t* tab;              // [images][huffman_batch_tab(nchunks)]
+    uint64_t* entry;            // [images][nchunks]
+    uint64_t* base;             // [images][nchunks]
+    uint32_t* count;            // [images][nchunks]
+    uint32_t* wgsum;            // [images][huffman_batch_wg(nchunks)]
+    uint32_t* E;                // [images][huffman_batch_entries()]
+    unsigned* flags;            // [images][2], zero before the launches: [0] symbols past out_pitch
+                                // (not written), [1] a bit string no code prefixes
+    uint64_t* total;            // [images] symbol counts
+    uint8_t* out;               // write: image k's symbols at out + k * out_pitch, at most out_pitch
+    size_t out_pitch;
+};
+size_t huffman_batch_tab(int nchunks);  // 16-bit table entries per image (a multiple of 8)
+uint32_t huffman_batch_wg(int nchunks);
+uint32_t huffman_batch_entries();
+// write = false: table pass, composition, counts, totals (returns the composition levels, < 0 on
+// error); write = true: the emit.
+int huffman_decode_images(const HufBatch& b, bool write, hipStream_t s);
+
 // P-frame of a gop > 1 video (ie_pframe.hip): one launch sequence per frame, chained on the device.
 struct PfArgs {
     const uint8_t* cur;      // the frame, rows cs apart

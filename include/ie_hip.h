@@ -60,6 +60,9 @@ enum {
 int ie_create(int device, ie_ctx** out);
 int ie_destroy(ie_ctx* ctx);
 const char* ie_last_error(const ie_ctx* ctx);
+/* Record msg as the context's last error: for a layer above this ABI (libie_host.so) whose callers
+ * read ie_last_error. */
+int ie_set_error(ie_ctx* ctx, const char* msg);
 /* Run on an external hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL restores
  * the context's own stream. */
 int ie_set_stream(ie_ctx* ctx, void* hip_stream);
@@ -271,6 +274,45 @@ int ie_huffman_table(const uint8_t* in, size_t len, uint64_t start_bit, uint16_t
 
 int ie_huffman_decode(ie_ctx* ctx, const uint8_t* in, size_t len, uint64_t start_bit, const uint16_t* lut,
                       uint8_t* out, size_t out_cap, size_t* nout);
+
+/* Huffman-decode `count` INDEPENDENT code streams in one set of launches (the decode half of
+ * ie_huffman_pack_batch; it replaces a loop of ie_huffman_decode calls, that is a loop over
+ * Huffman.cpp:354-402). Stream k is len[k] bytes at in + k*in_pitch; its code stream starts at bit
+ * start_bit[k] (just past its dictionary: the dictionaries differ in length) and is decoded to the
+ * END OF ITS BUFFER, padding bits included, exactly as ie_huffman_decode does. lut: count * 32768
+ * uint16 entries, image k's prefix table (ie_huffman_table) at 32768*k. Image k's symbols go to
+ * out + k*out_pitch, never past out_pitch bytes; nout[k] = its true symbol count, also when that
+ * exceeds out_pitch; the bytes of a slot past min(nout[k], out_pitch) are left untouched.
+ * len, start_bit, nout: host arrays of `count` entries. in, lut, out: host or device.
+ *  - IE_EINVAL: count < 1, len[k] > in_pitch, start_bit[k] > 8*len[k] (nothing is decoded).
+ *    start_bit[k] == 8*len[k] is an empty code stream: nout[k] = 0, no error.
+ *  - One synchronisation and one device-to-host read per call: every image's total and flag pair
+ *    come back together.  With a device `out` the symbols are written as they are decoded, before
+ *    the totals are known (bounded by out_pitch); a host `out` adds the copy of the symbols, never a
+ *    second table pass.
+ *  - An image holding a bit string no code prefixes makes the call return IE_EFORMAT, with
+ *    nout[k] = UINT64_MAX; an image with nout[k] > out_pitch makes it return IE_ECAP (the first
+ *    out_pitch symbols are there).  The call returns the code of the LOWEST failing k and
+ *    ie_last_error names that k; every other image's symbols and count are delivered as by a
+ *    successful call (the contract of ie_decode_images).
+ *  - A device `in` that is 4-byte aligned with in_pitch a multiple of 4 is read in place, and so
+ *    is a device lut; anything else is first copied into context scratch, from host memory only
+ *    the len[k] bytes of every image.
+ *  - One chunk plan serves the batch: the chunk count comes from the longest code stream, and a
+ *    shorter stream's trailing chunks hold no code.  Scratch is per image (about 2 bytes per stream
+ *    bit of the longest stream).  A batch whose scratch would exceed 1 GiB runs as sub-batches one
+ *    after another, still with one synchronisation at the end; the environment variable
+ *    IE_DEC_BATCH_MAX (read on every call) lowers the sub-batch size in images further. */
+int ie_huffman_decode_batch(ie_ctx* ctx, const uint8_t* in, size_t in_pitch, const uint64_t* len, int count,
+                            const uint64_t* start_bit, const uint16_t* lut,
+                            uint8_t* out, size_t out_pitch, uint64_t* nout);
+/* The same call, which also returns the first head_bytes (<= out_pitch) bytes of every output slot
+ * in host memory, heads + k*head_bytes, within the same synchronisation (ieh_decode_images reads
+ * the settings headers of the decoded streams this way; the bytes past nout[k] are whatever the
+ * slot held). */
+int ie_huffman_decode_batch_heads(ie_ctx* ctx, const uint8_t* in, size_t in_pitch, const uint64_t* len, int count,
+                                  const uint64_t* start_bit, const uint16_t* lut,
+                                  uint8_t* out, size_t out_pitch, uint64_t* nout, uint8_t* heads, size_t head_bytes);
 
 /* ---- Inverse path (ImageDecoder.cpp:55-122, Block.cpp:100-107,163-177,442-472) ------------
  * Decode nframes frames of block records starting at bit start_bit of `in` (len bytes) into

@@ -341,6 +341,22 @@ int64_t ieh_encode_video_gop(ie_ctx* ctx, const uint8_t* yuv, size_t len, int w,
 // call with cap = 0 to size the buffer.
 int64_t ieh_decode_image(ie_ctx* ctx, const uint8_t* enc, size_t len, int n, uint8_t* out, size_t cap, int* w,
                          int* h);
+/* Decode `count` image files that share their settings (quant matrix, rle, w, h) with block size n:
+ * file k is len[k] bytes at enc + k*enc_pitch (host memory); the pixels, w*h bytes per image back to
+ * back in file order, go to out (host or device, cap bytes).  Returns the pixel bytes, < 0 on error.
+ *  - Huffman-coded files: the dictionaries are parsed on the host (ie_huffman_table), ONE
+ *    ie_huffman_decode_batch call decodes every file into device slots, and ONE ie_decode_images
+ *    call reads those slots in place: the decoded streams never cross to the host, except the
+ *    first 256 bytes of each (its settings header), which ride with the symbol counts.  Two
+ *    synchronisations per call (plus ie_set_quant's when the matrix differs from the context's).
+ *  - Files without a dictionary (the "no gain" output, Huffman.cpp:329-341) form a second group,
+ *    read by ie_decode_images straight from the file bytes; a batch may mix both kinds.
+ *  - IE_EINVAL when a file's settings differ from file 0's; IE_EFORMAT for a malformed or truncated
+ *    file; ie_last_error names the file ("file k: ...").
+ *  - A cap below count*w*h returns IE_ECAP with *w / *h set, after the headers are known and before
+ *    any record decode (ieh_decode_image's convention). */
+int64_t ieh_decode_images(ie_ctx* ctx, const uint8_t* enc, size_t enc_pitch, const uint64_t* len, int count, int n,
+                          uint8_t* out, size_t cap, int* w, int* h);
 // Decode a gop=1 video file: frames of Y + w*h/2 bytes of 0x80 (Frame.cpp:121-124).  A cap
 // below the frames' size returns IE_ECAP after the header, as ieh_decode_image.
 int64_t ieh_decode_video(ie_ctx* ctx, const uint8_t* enc, size_t len, int n, uint8_t* out, size_t cap, int* w,
