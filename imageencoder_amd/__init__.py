@@ -72,6 +72,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ie_gop_stream_bound.restype = C.c_size_t
     L.ie_encode_gop.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_int, u8p, C.c_size_t, C.c_uint64, u64p, u64p]
+    if hasattr(L, "ie_encode_gop_groups"):  # (absent from an older IE_LIB build under comparison)
+        L.ie_encode_gop_groups.restype = C.c_int
+        L.ie_encode_gop_groups.argtypes = L.ie_encode_gop.argtypes
     L.ie_encode_images.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                    u8p, C.c_size_t, C.c_uint64, u64p]
     L.ie_encode_images_counted.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
@@ -383,13 +386,24 @@ class Codec:
         """The payload of a video with I- and P-frames (frame f is an I-frame when f % gop == 0;
         VideoEncoder.cpp:83-91, Frame.cpp:129-247) appended to ``out`` from ``start_bit``; ``out``
         holds :meth:`gop_stream_bound` bytes.  Returns ``(frame_bits, end_bit)``."""
+        return self._encode_gop(self.L.ie_encode_gop, y, w, h, out, gop, merange, start_bit, stride, frame_pitch,
+                                nframes, rle, mode)
+
+    def encode_gop_groups(self, y, w: int, h: int, out, gop: int, merange: int, start_bit: int = 0,
+                          stride: int | None = None, frame_pitch: int | None = None, nframes: int = 1,
+                          rle: bool = True, mode: int = MODE_FAST):
+        """:meth:`encode_gop` with the groups of pictures encoded side by side and spliced into the
+        same stream (ie_encode_gop_groups): same arguments, same bytes, same return value."""
+        return self._encode_gop(self.L.ie_encode_gop_groups, y, w, h, out, gop, merange, start_bit, stride,
+                                frame_pitch, nframes, rle, mode)
+
+    def _encode_gop(self, call, y, w, h, out, gop, merange, start_bit, stride, frame_pitch, nframes, rle, mode):
         stride = w if stride is None else stride
         frame_pitch = stride * h if frame_pitch is None else frame_pitch
         fb = np.zeros(nframes, dtype=np.uint64)
         end = C.c_uint64(0)
-        self._chk(self.L.ie_encode_gop(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, gop, merange, int(rle),
-                                       mode, _ptr(out), _nbytes(out), start_bit,
-                                       fb.ctypes.data_as(C.POINTER(C.c_uint64)), C.pointer(end)))
+        self._chk(call(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, gop, merange, int(rle), mode, _ptr(out),
+                       _nbytes(out), start_bit, fb.ctypes.data_as(C.POINTER(C.c_uint64)), C.pointer(end)))
         return fb, int(end.value)
 
     def decode_gop(self, stream, w: int, h: int, out, gop: int, merange: int, nframes: int, start_bit: int = 0,

@@ -204,7 +204,8 @@ int ie_destroy(ie_ctx* c) {
              c->d_tab, c->d_state, c->d_ticket, c->d_frame_start, c->d_chain_end, c->d_err, c->d_wave_fix, c->d_in, c->d_out,
              c->d_scratch, c->d_coef, c->d_code, c->d_hist, c->d_batch, c->d_chist, c->d_cslot[0], c->d_cslot[1], c->d_pack[0],
              c->d_pack[1], c->d_first, c->d_dec, c->d_walk, c->d_count, c->d_rtab, c->d_rpos, c->d_misc, c->d_imgbits,
-             c->d_hlut, c->d_hout, c->d_hufb, c->d_hufb_res, c->d_pix, c->d_gop_rec, c->d_gop_coef, c->d_gop_bits, c->d_gop_tile, c->d_gop_pos})
+             c->d_hlut, c->d_hout, c->d_hufb, c->d_hufb_res, c->d_pix, c->d_gop_rec, c->d_gop_coef, c->d_gop_bits, c->d_gop_tile, c->d_gop_pos,
+             c->d_gopg})
         if (d) (void)hipFree(d);
     for (void* h : std::initializer_list<void*>{c->h_tab, c->h_code, c->h_batch, c->h_hist[0], c->h_hist[1], c->h_pack[0],
                                                 c->h_pack[1], c->h_decres, c->h_imgres, c->h_hufb_res})

@@ -1,5 +1,6 @@
 // imageencoder_amd/csrc/ie_capi_encode.cpp -- the encode drivers of the C ABI: the launch of one
-// tile chain, the staged ie_encode_frames / ie_encode_images path, quantise-only, P-frame videos.
+// tile chain, the staged ie_encode_frames / ie_encode_images path, quantise-only, P-frame videos
+// frame by frame (ie_encode_gop) and with their groups of pictures side by side (ie_encode_gop_groups).
 #include "ie_ctx.hpp"
 
 using namespace iec;
@@ -202,6 +203,75 @@ size_t ie_gop_stream_bound(int w, int h, int n, int nframes, int merange, uint64
     return size_t((start_bit + per_frame * uint64_t(nframes) + 31) / 32) * 4 + 8;
 }
 
+}  // extern "C"
+
+namespace {
+
+// What ie_encode_gop and ie_encode_gop_groups check before any device work, in this order; gop is
+// already >= 1.  *need: ie_gop_stream_bound of the call.
+int check_gop(ie_ctx* c, int w, int h, size_t stride, size_t frame_pitch, int nframes, int gop, int merange,
+              size_t out_cap, uint64_t start_bit, size_t* need) {
+    int r = check_dims(c, w, h, nframes);  // (reported before a bad merange; check_frames passes it again)
+    if (r) return r;
+    if (merange < 0 || merange > 32767) return fail(c, IE_EINVAL, "merange must be in [0, 32767] (15-bit header field)");
+    if ((r = check_frames(c, w, h, nframes, stride, frame_pitch))) return r;
+    const bool has_p = gop > 1 && nframes > 1;
+    if (has_p && w % 16 && h / 16 >= 2)
+        return fail(c, IE_EINVAL, "P-frames need W % 16 == 0 when H >= 32: the reference builds its macroblocks "
+                                  "from misplaced, overlapping rows there (ImageBase.cpp:223-227)");
+    *need = ie_gop_stream_bound(w, h, c->n, nframes, merange, start_bit);
+    if (out_cap < *need) return fail(c, IE_ECAP, "output capacity below ie_gop_stream_bound");
+    return IE_OK;
+}
+
+// Where the P-frame payload is built: the caller's device stream, or zeroed staging (the P-frame
+// records are ORed in) holding the caller's leading bytes.  Word 0 of *dout = stream bytes [0, 4).
+int stage_gop_out(ie_ctx* c, uint8_t* out, bool out_dev, size_t need, uint64_t start_bit, uint32_t** dout) {
+    if (out_dev) {
+        if (reinterpret_cast<uintptr_t>(out) % 4) return fail(c, IE_EINVAL, "device output must be 4-byte aligned");
+        *dout = reinterpret_cast<uint32_t*>(out);
+        return IE_OK;
+    }
+    int r = ensure(c, c->d_out, c->cap_out, need);
+    if (r) return r;
+    HIPCHK(c, hipMemsetAsync(c->d_out, 0, need, c->stream));
+    const size_t hb = size_t((start_bit + 7) / 8);
+    if (hb) HIPCHK(c, hipMemcpyAsync(c->d_out, out, hb, hipMemcpyHostToDevice, c->stream));
+    *dout = reinterpret_cast<uint32_t*>(c->d_out);
+    return IE_OK;
+}
+
+// Before a P-frame video is redone in ticket mode on a device-resident stream: the first attempt
+// ORed vectors and P-frame records at positions derived from a bad end bit, so the caller's
+// stream is cleared from start_bit on (the bits before it are the caller's).
+int clear_gop_stream(ie_ctx* c, uint8_t* out, uint64_t start_bit, size_t need) {
+    const size_t b0 = size_t(start_bit / 8), b1 = size_t((start_bit + 7) / 8);
+    auto lead_bits = [&](bool set) {  // start_bit's byte (b1 > b0): its bits from start_bit on, set or cleared
+        uint8_t lead = 0;
+        HIPCHK(c, hipMemcpyAsync(&lead, out + b0, 1, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        lead = set ? lead | uint8_t(0xFFu >> (start_bit % 8)) : lead & uint8_t(0xFF00u >> (start_bit % 8));
+        HIPCHK(c, hipMemcpyAsync(out + b0, &lead, 1, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return int(IE_OK);
+    };
+    int r;
+    if (c->fake_fired) {  // debug: a faked timeout stands for a bad first attempt -- leave junk
+        c->fake_fired = false;
+        HIPCHK(c, hipMemsetAsync(out + b0 + (b1 > b0 ? 1 : 0), 0xA5, need - b1, c->stream));
+        if (b1 > b0 && (r = lead_bits(true))) return r;
+    }
+    if (need > b1) HIPCHK(c, hipMemsetAsync(out + b1, 0, need - b1, c->stream));
+    if (b1 > b0 && (r = lead_bits(false))) return r;
+    return IE_OK;
+}
+
+size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
+
+}  // namespace
+
+extern "C" {
+
 // The frame loop of VideoEncoder.cpp:83-91 with I- and P-frames (VideoBase.cpp:96-122): I-frames
 // through the block encoder, P-frames through ie_pframe.hip; every frame starts at the previous
 // frame's end bit read on the device, and a P-frame's reference is the previous frame's buffer as
@@ -210,34 +280,18 @@ int ie_encode_gop(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size
                   int merange, int use_rle, int mode, uint8_t* out, size_t out_cap, uint64_t start_bit,
                   uint64_t* frame_bits, uint64_t* end_bit) {
     if (!c || !y || !out) return IE_EINVAL;
-    int r = check_dims(c, w, h, nframes);  // (reported before a bad merange; check_frames passes it again)
-    if (r) return r;
     gop = std::max(1, gop);
-    if (merange < 0 || merange > 32767) return fail(c, IE_EINVAL, "merange must be in [0, 32767] (15-bit header field)");
-    if ((r = check_frames(c, w, h, nframes, stride, frame_pitch))) return r;
+    size_t need = 0;
+    int r = check_gop(c, w, h, stride, frame_pitch, nframes, gop, merange, out_cap, start_bit, &need);
+    if (r) return r;
     const bool has_p = gop > 1 && nframes > 1;
-    if (has_p && w % 16 && h / 16 >= 2)
-        return fail(c, IE_EINVAL, "P-frames need W % 16 == 0 when H >= 32: the reference builds its macroblocks "
-                                  "from misplaced, overlapping rows there (ImageBase.cpp:223-227)");
-    const size_t need = ie_gop_stream_bound(w, h, c->n, nframes, merange, start_bit);
-    if (out_cap < need) return fail(c, IE_ECAP, "output capacity below ie_gop_stream_bound");
     HIPCHK(c, hipSetDevice(c->device));
     const bool in_dev = is_device_ptr(y), out_dev = is_device_ptr(out);
 
     const uint8_t* dy;
     if ((r = stage_in(c, y, in_dev, frames_span(nframes, frame_pitch, stride, w, h), &dy))) return r;
     uint32_t* dout;
-    if (out_dev) {
-        if (reinterpret_cast<uintptr_t>(out) % 4) return fail(c, IE_EINVAL, "device output must be 4-byte aligned");
-        dout = reinterpret_cast<uint32_t*>(out);
-    } else {
-        // zeroed staging (the P-frame records are ORed in) holding the caller's leading bytes
-        if ((r = ensure(c, c->d_out, c->cap_out, need))) return r;
-        HIPCHK(c, hipMemsetAsync(c->d_out, 0, need, c->stream));
-        const size_t hb = size_t((start_bit + 7) / 8);
-        if (hb) HIPCHK(c, hipMemcpyAsync(c->d_out, out, hb, hipMemcpyHostToDevice, c->stream));
-        dout = reinterpret_cast<uint32_t*>(c->d_out);
-    }
+    if ((r = stage_gop_out(c, out, out_dev, need, start_bit, &dout))) return r;
     const int n = c->n, bx = w / n, nb = bx * (h / n);
     if (has_p) {
         if ((r = ensure(c, c->d_gop_rec, c->cap_gop_rec, 2 * size_t(w) * h))) return r;
@@ -299,27 +353,7 @@ int ie_encode_gop(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size
     bool redo;
     if ((r = ticket_redo(c, timeouts, &redo))) return r;
     if (redo) {  // an I-frame's tiles did not run in order: redo in ticket mode
-        if (out_dev) {
-            // the first attempt ORed vectors and P-frame records at positions derived from a bad end
-            // bit: clear the caller's stream from start_bit on (the bits before it are the caller's)
-            const size_t b0 = size_t(start_bit / 8), b1 = size_t((start_bit + 7) / 8);
-            auto lead_bits = [&](bool set) {  // start_bit's byte (b1 > b0): its bits from start_bit on, set or cleared
-                uint8_t lead = 0;
-                HIPCHK(c, hipMemcpyAsync(&lead, out + b0, 1, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                lead = set ? lead | uint8_t(0xFFu >> (start_bit % 8)) : lead & uint8_t(0xFF00u >> (start_bit % 8));
-                HIPCHK(c, hipMemcpyAsync(out + b0, &lead, 1, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                return int(IE_OK);
-            };
-            if (c->fake_fired) {  // debug: a faked timeout stands for a bad first attempt -- leave junk
-                c->fake_fired = false;
-                HIPCHK(c, hipMemsetAsync(out + b0 + (b1 > b0 ? 1 : 0), 0xA5, need - b1, c->stream));
-                if (b1 > b0 && (r = lead_bits(true))) return r;
-            }
-            if (need > b1) HIPCHK(c, hipMemsetAsync(out + b1, 0, need - b1, c->stream));
-            if (b1 > b0 && (r = lead_bits(false))) return r;
-        }
+        if (out_dev && (r = clear_gop_stream(c, out, start_bit, need))) return r;
         return ie_encode_gop(c, y, w, h, stride, frame_pitch, nframes, gop, merange, use_rle, mode, out, out_cap,
                              start_bit, frame_bits, end_bit);
     }
@@ -330,6 +364,151 @@ int ie_encode_gop(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size
     if (frame_bits)
         for (int f = 0; f < nframes; f++) frame_bits[f] = pos[f + 1] - pos[f];
     if (end_bit) *end_bit = pos[nframes];
+    return IE_OK;
+}
+
+// ie_encode_gop with the groups of pictures side by side.  An I-frame resets the prediction, so a
+// group takes nothing from its predecessors but the bit its payload starts at: every group is
+// encoded into a zeroed slot of its own from bit 0 -- step 0 the I-frames as one batch of
+// independent images (the launch of ie_encode_images), step j the j-th frame of every group that
+// has one (launch_pframe_groups: always a prefix of the groups) -- and gop_splice_kernel moves the
+// slots' payloads end to end into the stream.  The launch sequence is as deep as gop, not nframes.
+int ie_encode_gop_groups(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,
+                         int gop, int merange, int use_rle, int mode, uint8_t* out, size_t out_cap, uint64_t start_bit,
+                         uint64_t* frame_bits, uint64_t* end_bit) {
+    if (!c || !y || !out) return IE_EINVAL;
+    if (gop <= 1 || nframes <= gop)  // no P-frame, or one group: nothing to run side by side
+        return ie_encode_gop(c, y, w, h, stride, frame_pitch, nframes, gop, merange, use_rle, mode, out, out_cap,
+                             start_bit, frame_bits, end_bit);
+    size_t need = 0;
+    int r = check_gop(c, w, h, stride, frame_pitch, nframes, gop, merange, out_cap, start_bit, &need);
+    if (r) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool in_dev = is_device_ptr(y), out_dev = is_device_ptr(out);
+    const uint8_t* dy;
+    if ((r = stage_in(c, y, in_dev, frames_span(nframes, frame_pitch, stride, w, h), &dy))) return r;
+    uint32_t* dout;
+    if ((r = stage_gop_out(c, out, out_dev, need, start_bit, &dout))) return r;
+
+    // Scratch per group: the slot, two reconstructed frames, the prediction error's coefficients
+    // (4x4 only) and record lengths, the tile sums, and its column of the position table; a video
+    // that would need more than 1 GiB (or 65535 groups: grid.y) runs as waves of groups that share
+    // the scratch in stream order (IE_GOP_BATCH_MAX, read on every call, lowers their size further).
+    const int n = c->n, bx = w / n, nb = bx * (h / n), G = (nframes + gop - 1) / gop;
+    const size_t fpx = size_t(w) * h;
+    const size_t sz_slot = align256(ie_gop_stream_bound(w, h, n, gop, merange, 0)), sz_rec = align256(2 * fpx);
+    const size_t sz_coef = n == 4 ? align256(size_t(nb) * 16 * sizeof(int16_t)) : 0;
+    const size_t sz_bits = align256(size_t(nb) * sizeof(uint32_t));
+    const size_t sz_tile = align256((size_t(ie::pframe_tiles(nb)) + 1) * sizeof(uint64_t));
+    const size_t per_group = sz_slot + sz_rec + sz_coef + sz_bits + sz_tile + (size_t(gop) + 2) * sizeof(uint64_t);
+    size_t Gw = std::min<size_t>({size_t(G), 65535, std::max<size_t>(1, ((size_t(1) << 30) - 1024) / per_group)});
+    if (const char* eb = getenv("IE_GOP_BATCH_MAX"))  // (read on every call: a limit in groups, only ever lower)
+        if (atoll(eb) > 0) Gw = std::min<size_t>(Gw, size_t(atoll(eb)));
+    const size_t sz_pos = align256((size_t(gop) + 1) * Gw * sizeof(uint64_t));
+    const size_t sz_goff = align256((Gw + 1) * sizeof(uint64_t));
+    if ((r = ensure(c, c->d_gopg, c->cap_gopg, Gw * (per_group - (size_t(gop) + 2) * sizeof(uint64_t)) + sz_pos + sz_goff)))
+        return r;
+    uint8_t* p = c->d_gopg;
+    auto carve = [&p](size_t bytes) {
+        uint8_t* q = p;
+        p += bytes;
+        return q;
+    };
+    uint32_t* const slots = reinterpret_cast<uint32_t*>(carve(Gw * sz_slot));
+    uint8_t* const rec = carve(Gw * sz_rec);
+    int16_t* const coef = reinterpret_cast<int16_t*>(carve(Gw * sz_coef));
+    uint32_t* const bits = reinterpret_cast<uint32_t*>(carve(Gw * sz_bits));
+    uint64_t* const tile = reinterpret_cast<uint64_t*>(carve(Gw * sz_tile));
+    uint64_t* const pos = reinterpret_cast<uint64_t*>(carve(sz_pos));  // [gop + 1][groups of the wave]
+    uint64_t* const goff = reinterpret_cast<uint64_t*>(carve(sz_goff));
+    if ((r = ensure(c, c->d_gop_pos, c->cap_gop_pos, size_t(nframes) + 1))) return r;
+
+    for (int g0 = 0; g0 < G; g0 += int(Gw)) {
+        const int gw = std::min(int(Gw), G - g0);
+        const int f0 = g0 * gop;  // (< nframes)
+        const int nfw = int(std::min<int64_t>(int64_t(nframes) - f0, int64_t(gw) * gop));
+        const uint8_t* wy = dy + size_t(f0) * frame_pitch;
+        const size_t group_pitch = size_t(gop) * frame_pitch;
+        HIPCHK(c, hipMemsetAsync(slots, 0, size_t(gw) * sz_slot, c->stream));
+        HIPCHK(c, hipMemsetAsync(pos, 0, size_t(gw) * sizeof(uint64_t), c->stream));  // every slot starts at bit 0
+        {  // step 0: the I-frames, a batch of independent images; their end bits are pos[1][g]
+            Launch L(wy, w, h, stride, group_pitch, gw, use_rle, mode, slots, 0);
+            L.segmented = 1;
+            L.out_pitch = sz_slot;
+            L.chain_end = pos + gw;
+            if ((r = launch_chain(c, L))) return r;
+        }
+        for (int j = 1; j < gop && j < nfw; j++) {  // step j: frame j of the groups that have one
+            ie::PfArgs a{};
+            a.cur = wy + size_t(j) * frame_pitch;
+            a.cs = stride;
+            a.g_cur = group_pitch;
+            if (j == 1) {  // the I-frame as the caller holds it
+                a.ref = wy;
+                a.rs = stride;
+                a.g_ref = group_pitch;
+            } else {       // the previous P-frame's reconstruction
+                a.ref = rec + size_t((j - 1) & 1) * fpx;
+                a.rs = size_t(w);
+                a.g_ref = sz_rec;
+            }
+            a.rec = rec + size_t(j & 1) * fpx;
+            a.g_rec = sz_rec;
+            a.w = w;
+            a.h = h;
+            a.mbx = w / 16;
+            a.mby = h / 16;
+            a.bx = bx;
+            a.rle = use_rle ? 1 : 0;
+            a.merange = merange;
+            a.mv_bits = mvec_bits(merange);
+            a.tab = c->d_tab;
+            a.coef = coef;
+            a.g_coef = sz_coef / sizeof(int16_t);
+            a.bits = bits;
+            a.g_bits = sz_bits / sizeof(uint32_t);
+            a.g_tile = sz_tile / sizeof(uint64_t);
+            a.out = slots;
+            a.g_out = sz_slot / sizeof(uint32_t);
+            a.start = pos + size_t(j) * gw;
+            a.end = pos + size_t(j + 1) * gw;
+            const int gj = std::min(gw, (nfw - j + gop - 1) / gop);
+            ie::launch_pframe_groups(a, n, gj, tile, c->stream);
+            HIPCHK(c, hipGetLastError());
+        }
+        ie::GopSplice sp{};
+        sp.pos = pos;
+        sp.groups = gw;
+        sp.gop = gop;
+        sp.nframes = nfw;
+        sp.slots = slots;
+        sp.slot_words = sz_slot / sizeof(uint32_t);
+        sp.out = dout;
+        sp.base = start_bit;
+        sp.base_dev = g0 ? c->d_gop_pos + f0 : nullptr;  // the previous wave's end bit
+        sp.goff = goff;
+        sp.fpos = c->d_gop_pos + f0;
+        ie::launch_gop_splice(sp, c->stream);
+        HIPCHK(c, hipGetLastError());
+    }
+    std::vector<uint64_t> fp(size_t(nframes) + 1);
+    HIPCHK(c, hipMemcpyAsync(fp.data(), c->d_gop_pos, fp.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    unsigned timeouts = 0;
+    if ((r = read_errors(c, &timeouts, nullptr))) return r;  // the call's one synchronisation
+    bool redo;
+    if ((r = ticket_redo(c, timeouts, &redo))) return r;
+    if (redo) {  // an I-frame batch's tiles did not run in order: redo in ticket mode
+        if (out_dev && (r = clear_gop_stream(c, out, start_bit, need))) return r;
+        return ie_encode_gop_groups(c, y, w, h, stride, frame_pitch, nframes, gop, merange, use_rle, mode, out, out_cap,
+                                    start_bit, frame_bits, end_bit);
+    }
+    if (!out_dev) {
+        const size_t b0 = size_t(start_bit / 8), b1 = size_t((fp[nframes] + 7) / 8);
+        HIPCHK(c, hipMemcpy(out + b0, c->d_out + b0, b1 - b0, hipMemcpyDeviceToHost));
+    }
+    if (frame_bits)
+        for (int f = 0; f < nframes; f++) frame_bits[f] = fp[f + 1] - fp[f];
+    if (end_bit) *end_bit = fp[nframes];
     return IE_OK;
 }
 

@@ -186,6 +186,11 @@ struct ie_ctx {
     size_t cap_gop_tile = 0;
     uint64_t* d_gop_pos = nullptr;
     size_t cap_gop_pos = 0;
+    // ie_encode_gop_groups: one wave of groups' scratch, carved per kind (every group's slot, then
+    // every group's reconstructed frames, coefficients, record lengths, tile sums; the wave's
+    // position table and the groups' first bits).  The frames' positions in the stream: d_gop_pos.
+    uint8_t* d_gopg = nullptr;
+    size_t cap_gopg = 0;
 };
 
 namespace iec {

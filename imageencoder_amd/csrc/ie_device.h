@@ -333,8 +333,32 @@ struct PfArgs {
     uint64_t* st;            // record tiles' chain state (look-back scan); nullptr = separate scan launches
     uint32_t tag;            // the state's epoch
     unsigned* err;           // [0]: look-back spin timeouts
+    // Group batch (launch_pframe_groups: blockIdx.y = the group).  Group g's frame, reference,
+    // buffer, coefficients, record lengths, tile sums and output slot lie g times these strides (in
+    // elements of each array) past the pointers above, its first / end bit in start[g] / end[g].
+    // All 0 with one group: the single-frame launch.
+    uint64_t g_cur, g_ref, g_rec, g_coef, g_bits, g_tile, g_out;
 };
 void launch_pframe(const PfArgs& a, int n, uint64_t* tile_scratch, hipStream_t s);
+// The same P-frame of `groups` independent groups of pictures in one set of launches (the g_
+// strides set, a.st ignored): macroblocks, then tile sums / tile scan / emission in every mode --
+// no look-back chain per group.  groups <= 65535 (grid.y).
+void launch_pframe_groups(const PfArgs& a, int n, int groups, uint64_t* tile_scratch, hipStream_t s);
+
+// Splice of a video's groups of pictures (ie_encode_gop_groups): group g's private slot (bits
+// [0, len_g) from slots + g * slot_words) goes to out at bit base + sum_{k<g} len_k.
+struct GopSplice {
+    const uint64_t* pos;     // [gop + 1][groups]: pos[j * groups + g] = first bit of group g's frame j in its slot
+    int groups, gop, nframes;  // of this wave; nframes <= groups * gop (only the last group can be short)
+    const uint32_t* slots;
+    uint64_t slot_words;
+    uint32_t* out;           // zero from the base bit on
+    uint64_t base;           // the wave's first bit in out ...
+    const uint64_t* base_dev;  // ... or, when non-null, *base_dev (the previous wave's end bit)
+    uint64_t* goff;          // [groups + 1] scratch: every group's first bit in out, then the wave's end
+    uint64_t* fpos;          // [nframes + 1]: every frame's first bit in out, then the wave's end
+};
+void launch_gop_splice(const GopSplice& a, hipStream_t s);
 // P-frame decode, first half (Block.cpp:481-496): every macroblock's motion vector read from the
 // stream words (big-endian bytes) at start_bit, the previous decoded frame's block at the clamped
 // vector copied into place

@@ -14,7 +14,9 @@
 // the 4x4 microblocks' error and the FP64 transform rows staged in LDS.  The FP64 arithmetic is the reference's operation
 // order (compiled with -ffp-contract=off).  The frame's first bit lives on the device (the
 // previous frame's end), so consecutive frames chain without a host round trip; the records are
-// placed by a two-level scan of their lengths and ORed into the zeroed stream.
+// placed by a two-level scan of their lengths and ORed into the zeroed stream.  The same kernels
+// run one frame of many groups of pictures at once (blockIdx.y = the group, each with a stream slot
+// of its own); gop_splice_kernel then moves the slots' payloads end to end (ie_encode_gop_groups).
 #include <hip/hip_runtime.h>
 
 #include "ie_common.hpp"
@@ -109,6 +111,20 @@ __device__ __forceinline__ uint32_t load4(const uint8_t* p) {
     return uint32_t(p[0]) | (uint32_t(p[1]) << 8) | (uint32_t(p[2]) << 16) | (uint32_t(p[3]) << 24);
 }
 
+// The group's view of a batched launch (launch_pframe_groups: blockIdx.y = the group of pictures).
+// Wave-uniform address arithmetic only; with one group and strides of 0 it changes nothing.
+__device__ __forceinline__ void pf_group(PfArgs& a) {
+    const uint64_t g = blockIdx.y;
+    a.cur += g * a.g_cur;
+    a.ref += g * a.g_ref;
+    a.rec += g * a.g_rec;
+    a.coef += g * a.g_coef;
+    a.bits += g * a.g_bits;
+    a.out += g * a.g_out;
+    a.start += g;
+    a.end += g;
+}
+
 // Pixels no macroblock covers (the bottom strip, rows [16*mby, h), then the right strip of the
 // covered rows, columns [16*mbx, w)): their microblocks keep the frame's own pixels as "error" and
 // have no record (bits = 0, written here for 4x4 blocks), so expandDifferences doubles them
@@ -145,6 +161,7 @@ __global__ __launch_bounds__(kMbTPB) void pf_macroblock_kernel(PfArgs a) {
     __shared__ int16_t cq[256];
     const int l = threadIdx.x;
     const int mb = blockIdx.x;
+    pf_group(a);
     if (mb >= a.mbx * a.mby) {
         const size_t i = size_t(mb - a.mbx * a.mby) * kMbTPB + size_t(l);
         const size_t npx = size_t(a.w) * a.h - size_t(a.mbx) * a.mby * kMB * kMB;
@@ -294,8 +311,11 @@ __device__ __forceinline__ uint64_t block_exscan(uint64_t v, uint64_t* sh, uint6
     return before + x - v;
 }
 
-__global__ __launch_bounds__(kTPB) void pf_tile_sum_kernel(const uint32_t* bits, int nb, uint64_t* tsum) {
+__global__ __launch_bounds__(kTPB) void pf_tile_sum_kernel(const uint32_t* bits, int nb, uint64_t* tsum, uint64_t g_bits,
+                                                           uint64_t g_tile) {
     __shared__ uint64_t sh[kTPB / 64];
+    bits += blockIdx.y * g_bits;  // (the group of a batched launch)
+    tsum += blockIdx.y * g_tile;
     const int b0 = blockIdx.x * kPfTileBlocks + threadIdx.x * kPfPer;
     uint64_t s = 0;
     for (int k = 0; k < kPfPer; k++)
@@ -305,10 +325,13 @@ __global__ __launch_bounds__(kTPB) void pf_tile_sum_kernel(const uint32_t* bits,
     if (threadIdx.x == 0) tsum[blockIdx.x] = tot;
 }
 
-// one workgroup: exclusive prefix of the tile sums; the frame's end bit
+// one workgroup (per group of a batched launch): exclusive prefix of the tile sums; the frame's end bit
 __global__ __launch_bounds__(kTPB) void pf_tile_scan_kernel(uint64_t* tsum, int ntiles, uint64_t head_bits,
-                                                            const uint64_t* start, uint64_t* end) {
+                                                            const uint64_t* start, uint64_t* end, uint64_t g_tile) {
     __shared__ uint64_t sh[kTPB / 64];
+    tsum += blockIdx.y * g_tile;
+    start += blockIdx.y;
+    end += blockIdx.y;
     uint64_t carry = 0;
     for (int t0 = 0; t0 < ntiles; t0 += kTPB) {
         const int i = t0 + threadIdx.x;
@@ -329,6 +352,8 @@ __global__ __launch_bounds__(kTPB) void pf_emit_kernel(PfArgs a, int nb, const u
     __shared__ uint64_t sh[kTPB / 64];
     __shared__ uint32_t img[kPfImgWords];
     const int t = threadIdx.x;
+    pf_group(a);
+    tpre += blockIdx.y * a.g_tile;
     const int b0 = blockIdx.x * kPfTileBlocks + t * kPfPer;
     uint64_t s = 0;
     for (int k = 0; k < kPfPer; k++)
@@ -415,9 +440,58 @@ __global__ __launch_bounds__(kTPB) void pf_emit_chain_kernel(PfArgs a, int nb, i
     }
 }
 
-// the frame's end bit when it carries no records (8x8 blocks, or no macroblock)
+// the frame's end bit when it carries no records (8x8 blocks, or no macroblock); blockIdx.y = the group
 __global__ void pf_end_kernel(const uint64_t* start, uint64_t* end, uint64_t head_bits) {
-    if (threadIdx.x == 0) *end = *start + head_bits;
+    if (threadIdx.x == 0) end[blockIdx.y] = start[blockIdx.y] + head_bits;
+}
+
+// ---- the splice of ie_encode_gop_groups: every group of pictures was encoded into a slot of its
+// own from bit 0; the video's stream is the slots' payloads end to end.
+
+// One workgroup: the exclusive scan of the groups' lengths (256 groups a round) gives every
+// group's first bit in the stream; the same threads fill the frames' position table.
+__global__ __launch_bounds__(kTPB) void gop_splice_scan_kernel(GopSplice a) {
+    __shared__ uint64_t sh[kTPB / 64];
+    uint64_t carry = a.base_dev ? *a.base_dev : a.base;
+    for (int g0 = 0; g0 < a.groups; g0 += kTPB) {
+        const int g = g0 + int(threadIdx.x);
+        int nf = 0;  // the group's frames (only the last group can be short)
+        uint64_t len = 0;
+        if (g < a.groups) {
+            nf = int(min(int64_t(a.gop), int64_t(a.nframes) - int64_t(g) * a.gop));
+            len = a.pos[size_t(nf) * a.groups + g];
+        }
+        uint64_t tot;
+        const uint64_t D = carry + block_exscan(len, sh, &tot);
+        if (g < a.groups) {
+            a.goff[g] = D;
+            for (int j = 0; j < nf; j++) a.fpos[size_t(g) * a.gop + j] = D + a.pos[size_t(j) * a.groups + g];
+        }
+        carry += tot;
+    }
+    if (threadIdx.x == 0) a.goff[a.groups] = a.fpos[a.nframes] = carry;
+}
+
+// blockIdx.y = the group; a workgroup owns runs of 256 consecutive destination words of it.
+// Destination word i of a group that starts `sh` bits into a word is the 32 bits from bit
+// 32 i - sh of its slot: two adjacent slot words (MSB-first after the byte swap) through one funnel
+// shift.  The slot is zero past the group's last bit and has two spare words, so the last word needs
+// no mask.  A group's first and last word may be shared with its neighbours (with tiny frames
+// several groups share one word) and with the caller's bits before the stream: those are ORed, the
+// words between are the group's alone and are stored.  No workgroup waits for another.
+__global__ __launch_bounds__(kTPB) void gop_splice_kernel(GopSplice a) {
+    const uint32_t g = blockIdx.y;
+    const uint64_t D = a.goff[g], len = a.goff[g + 1] - D;
+    const uint32_t sh = uint32_t(D & 31u);
+    const uint64_t nw = (sh + len + 31) >> 5;
+    const uint32_t* src = a.slots + uint64_t(g) * a.slot_words;
+    uint32_t* dst = a.out + (D >> 5);
+    for (uint64_t i = uint64_t(blockIdx.x) * kTPB + threadIdx.x; i < nw; i += uint64_t(gridDim.x) * kTPB) {
+        const uint32_t hi = i ? bswap32(src[i - 1]) : 0u;
+        const uint32_t v = bswap32(__builtin_amdgcn_alignbit(hi, bswap32(src[i]), sh));
+        if (i == 0 || i == nw - 1) atomicOr(dst + i, v);
+        else dst[i] = v;
+    }
 }
 
 // P-frame decode, first half: lane l copies row l/4, pixels 4(l%4)..+3 of the reference block
@@ -455,27 +529,39 @@ void launch_pframe_mvcopy(const uint8_t* stream, uint64_t start_bit, const uint6
                            rs, out, os, w, h, w / kMB);
 }
 
-void launch_pframe(const PfArgs& a, int n, uint64_t* tsum, hipStream_t s) {
+void launch_pframe(const PfArgs& a, int n, uint64_t* tsum, hipStream_t s) { launch_pframe_groups(a, n, 1, tsum, s); }
+
+void launch_gop_splice(const GopSplice& a, hipStream_t s) {
+    hipLaunchKernelGGL(gop_splice_scan_kernel, dim3(1), dim3(kTPB), 0, s, a);
+    // enough workgroups for the longest possible group, at most about 2048 in all (the rest loops)
+    const uint64_t rounds = (a.slot_words + kTPB) / kTPB;
+    const unsigned gx = unsigned(std::min<uint64_t>(rounds, std::max(1, 2048 / a.groups)));
+    hipLaunchKernelGGL(gop_splice_kernel, dim3(gx, unsigned(a.groups)), dim3(kTPB), 0, s, a);
+}
+
+void launch_pframe_groups(const PfArgs& a, int n, int groups, uint64_t* tsum, hipStream_t s) {
+    const unsigned gy = unsigned(groups);
     const int nmb = a.mbx * a.mby;
     const uint64_t head = uint64_t(nmb) * 2u * uint32_t(a.mv_bits);
     const int nb = a.bx * (a.h / n);
     const size_t px = size_t(a.w) * a.h - size_t(nmb) * kMB * kMB;  // pixels no macroblock covers
     const unsigned grid = unsigned(nmb) + unsigned((px + kMbTPB - 1) / kMbTPB);  // + the strips' workgroups
     if (grid) {
-        if (n == 4) hipLaunchKernelGGL(pf_macroblock_kernel<4>, dim3(grid), dim3(kMbTPB), 0, s, a);
-        else hipLaunchKernelGGL(pf_macroblock_kernel<8>, dim3(grid), dim3(kMbTPB), 0, s, a);
+        if (n == 4) hipLaunchKernelGGL(pf_macroblock_kernel<4>, dim3(grid, gy), dim3(kMbTPB), 0, s, a);
+        else hipLaunchKernelGGL(pf_macroblock_kernel<8>, dim3(grid, gy), dim3(kMbTPB), 0, s, a);
     }
     if (n == 4 && nmb > 0) {
         const int ntiles = (nb + kPfTileBlocks - 1) / kPfTileBlocks;
-        if (a.st) {  // one launch: the scan by look-back
+        if (a.st) {  // one launch: the scan by look-back (single frames only: the batch leaves st null)
             hipLaunchKernelGGL(pf_emit_chain_kernel, dim3(ntiles), dim3(kTPB), 0, s, a, nb, ntiles, head);
-        } else {     // (ticket mode: tiles may not run in dispatch order) tile sums, scan, emission
-            hipLaunchKernelGGL(pf_tile_sum_kernel, dim3(ntiles), dim3(kTPB), 0, s, a.bits, nb, tsum);
-            hipLaunchKernelGGL(pf_tile_scan_kernel, dim3(1), dim3(kTPB), 0, s, tsum, ntiles, head, a.start, a.end);
-            hipLaunchKernelGGL(pf_emit_kernel, dim3(ntiles), dim3(kTPB), 0, s, a, nb, tsum, head);
+        } else {     // (ticket mode: tiles may not run in dispatch order; every batch) tile sums, scan, emission
+            hipLaunchKernelGGL(pf_tile_sum_kernel, dim3(ntiles, gy), dim3(kTPB), 0, s, a.bits, nb, tsum, a.g_bits, a.g_tile);
+            hipLaunchKernelGGL(pf_tile_scan_kernel, dim3(1, gy), dim3(kTPB), 0, s, tsum, ntiles, head, a.start, a.end,
+                               a.g_tile);
+            hipLaunchKernelGGL(pf_emit_kernel, dim3(ntiles, gy), dim3(kTPB), 0, s, a, nb, tsum, head);
         }
     } else {
-        hipLaunchKernelGGL(pf_end_kernel, dim3(1), dim3(64), 0, s, a.start, a.end, head);
+        hipLaunchKernelGGL(pf_end_kernel, dim3(1, gy), dim3(64), 0, s, a.start, a.end, head);
     }
 }
 

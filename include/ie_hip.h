@@ -116,6 +116,32 @@ int ie_encode_gop(ie_ctx* ctx, const uint8_t* y, int w, int h, size_t stride, si
                   int gop, int merange, int use_rle, int mode, uint8_t* out, size_t out_cap, uint64_t start_bit,
                   uint64_t* frame_bits, uint64_t* end_bit);
 
+/* ie_encode_gop with the video's groups of pictures encoded side by side: the same arguments, the
+ * same ie_gop_stream_bound() capacity, host or device y and out, the same checks in the same order
+ * with the same codes, and the same out bytes, frame_bits[] and *end_bit, bit for bit.  An I-frame
+ * resets the prediction, so group g (frames g*gop .. g*gop + gop - 1) takes nothing from the groups
+ * before it but the bit its payload starts at.  With G = ceil(nframes / gop) groups:
+ *  - step 0 encodes the G I-frames as one batch of independent images (the launch of
+ *    ie_encode_images), step j = 1 .. gop - 1 the j-th frame of every group that has one (one set
+ *    of P-frame launches whose second grid dimension is the group); every group writes a private,
+ *    zeroed slot of ie_gop_stream_bound(w, h, n, gop, merange, 0) bytes from bit 0;
+ *  - a splice moves group g's bits to out at start_bit + the lengths of the groups before it
+ *    (interior words stored, a group's first and last word ORed: out must be zero from start_bit
+ *    on, the rule above) and fills the frames' position table.
+ * The launch sequence is as deep as gop, not nframes.  One host synchronisation per call: the read
+ * of the position table and the error counters.  A look-back timeout in an I-frame batch is
+ * handled as in ie_encode_gop (a device out cleared from start_bit on, the video redone in ticket
+ * mode).  Scratch per group: the slot, two reconstructed frames (2*w*h bytes), 32 bytes of
+ * coefficients and 4 bytes of record length per 4x4 block, the record tiles' sums.  A video whose
+ * scratch would exceed 1 GiB (or with more than 65535 groups) runs as waves of groups, one after
+ * another on the stream, each wave's splice starting at the previous wave's end bit read on the
+ * device -- still one synchronisation at the end; the environment variable IE_GOP_BATCH_MAX (read
+ * on every call) lowers the wave size in groups further.  With gop <= 1 or fewer than two groups
+ * the call is ie_encode_gop. */
+int ie_encode_gop_groups(ie_ctx* ctx, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,
+                         int gop, int merange, int use_rle, int mode, uint8_t* out, size_t out_cap, uint64_t start_bit,
+                         uint64_t* frame_bits, uint64_t* end_bit);
+
 /* Encode nframes INDEPENDENT images in one launch (an image-server batch): image f's records
  * go to out + f*out_pitch from bit start_bit (each image carries its own header region).
  * end_bits optional [nframes].  out_pitch must be a multiple of 4 bytes. */
