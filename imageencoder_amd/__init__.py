@@ -112,6 +112,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ie_host_free.argtypes = [vp, vp]
     L.ie_vstream_open.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, u8p, C.c_uint64,
                                   C.c_int, C.POINTER(C.c_void_p)]
+    if hasattr(L, "ie_vstream_open_gop"):  # (absent from an older IE_LIB build under comparison)
+        L.ie_vstream_open_gop.restype = C.c_int
+        L.ie_vstream_open_gop.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, u8p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
     L.ie_vstream_push.argtypes = [vp, u8p, C.c_int]
     L.ie_vstream_pull.argtypes = [vp, u8p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.ie_vstream_finish.argtypes = [vp, u8p, C.c_size_t, C.POINTER(C.c_size_t), u64p, u64p]
@@ -247,7 +251,7 @@ class _PinnedOwner:
 class VideoStream:
     """ie_vstream_*: push host frames, pull finished stream bytes, finish (see include/ie_hip.h)."""
 
-    def __init__(self, codec, w, h, head, start_bit, max_frames, stride, frame_pitch, rle, mode):
+    def __init__(self, codec, w, h, head, start_bit, max_frames, stride, frame_pitch, rle, mode, gop=1, merange=0):
         self.c = codec
         self.w, self.h = w, h
         self.stride = w if stride is None else stride
@@ -255,12 +259,13 @@ class VideoStream:
         head = np.zeros(1, dtype=np.uint8) if head is None else np.ascontiguousarray(head, dtype=np.uint8)
         self._head = head
         v = C.c_void_p()
-        codec._chk(codec.L.ie_vstream_open(codec.h, w, h, self.stride, self.frame_pitch, int(rle), mode,
-                                           head.ctypes.data, start_bit, max_frames, C.byref(v)))
+        codec._chk(codec.L.ie_vstream_open_gop(codec.h, w, h, self.stride, self.frame_pitch, gop, merange, int(rle),
+                                               mode, head.ctypes.data, start_bit, max_frames, C.byref(v)))
         self.v = v
         self.max_frames = max_frames
         self.pushed = 0
-        self.cap = stream_bound(w, h, codec.n, max_frames, start_bit)
+        self.cap = (codec.gop_stream_bound(w, h, max_frames, merange, start_bit) if gop > 1
+                    else stream_bound(w, h, codec.n, max_frames, start_bit))
 
     def push(self, frames, nframes: int):
         self.c._chk(self.c.L.ie_vstream_push(self.v, _ptr(frames), nframes))
@@ -459,10 +464,11 @@ class Codec:
 
     def open_video_stream(self, w: int, h: int, head=None, start_bit: int = 0, max_frames: int = 1,
                           stride: int | None = None, frame_pitch: int | None = None, rle: bool = True,
-                          mode: int = MODE_FAST) -> "VideoStream":
-        """ie_vstream_open: a gop=1 video payload grown on the device from host frames pushed over
-        time (Frame.cpp:31-45 / VideoEncoder.cpp:83-91)."""
-        return VideoStream(self, w, h, head, start_bit, max_frames, stride, frame_pitch, rle, mode)
+                          mode: int = MODE_FAST, gop: int = 1, merange: int = 0) -> "VideoStream":
+        """ie_vstream_open_gop: a video payload grown on the device from host frames pushed over
+        time (Frame.cpp:31-45 / VideoEncoder.cpp:83-91); with gop > 1 the video has P-frames and is
+        encoded in chunks of whole groups of pictures (the stream equals encode_gop's)."""
+        return VideoStream(self, w, h, head, start_bit, max_frames, stride, frame_pitch, rle, mode, gop, merange)
 
     def end_bits_into(self, dst, count: int = 1):
         """Stream-ordered device copy of the last encode's end bit(s) (one per chain) into the

@@ -111,9 +111,9 @@ int encode_file(ie_ctx* c, const uint8_t* y, const FileParams& p, std::vector<ui
     if ((r = ie_memset(c, s.enc.p, 0, pframes ? cap : hb + 4))) return (err = ie_last_error(c), r);
     if ((r = ie_memcpy(c, s.enc.p, hdr.get_buffer(), hb))) return (err = ie_last_error(c), r);
     uint64_t end = 0;
-    if (pframes) {
-        if ((r = ie_encode_gop(c, y, p.w, p.h, size_t(p.w), p.frame_pitch, p.frames, p.gop, p.merange, p.rle ? 1 : 0,
-                               p.mode, s.enc.p, s.enc.cap, H, nullptr, &end)))
+    if (pframes) {  // the groups of pictures side by side: ie_encode_gop's bytes, a launch chain as deep as gop
+        if ((r = ie_encode_gop_groups(c, y, p.w, p.h, size_t(p.w), p.frame_pitch, p.frames, p.gop, p.merange,
+                                      p.rle ? 1 : 0, p.mode, s.enc.p, s.enc.cap, H, nullptr, &end)))
             return (err = ie_last_error(c), r);
     } else if ((r = ie_encode_frames(c, y, p.w, p.h, size_t(p.w), p.frame_pitch, p.frames, p.rle ? 1 : 0, p.mode,
                                      s.enc.p, s.enc.cap, H, nullptr, &end)))
@@ -131,12 +131,15 @@ int encode_file(ie_ctx* c, const uint8_t* y, const FileParams& p, std::vector<ui
     return IE_OK;
 }
 
-// A gop=1 video file encoded while it is read: frame chunks go from the .raw/YUV420 file into two
+// A video file encoded while it is read: frame chunks go from the .raw/YUV420 file into two
 // page-locked buffers in turn (VideoBase.cpp:6-19 and utils.hpp:352-376 read the whole file
 // first), each chunk is pushed to an ie_vstream -- copied to the device and encoded behind the
-// previous chunk on the device's chain -- while the host reads the next one, and the finished
-// bytes are pulled out as the chunks complete.  With Huffman the stream stays on the device for
-// the Huffman pass over the whole file (Huffman.cpp:233-344 needs every byte's count first).
+// previous chunk on the device's chain (with P-frames, gop > 1: whole groups of pictures side by
+// side, ie_vstream_open_gop) -- while the host reads the next one, and the finished bytes are
+// pulled out as the chunks complete.  The host holds two read buffers and the device two input
+// slots, one wave of scratch and the output stream, never the whole video.  With Huffman the
+// stream stays on the device for the Huffman pass over the whole file (Huffman.cpp:233-344 needs
+// every byte's count first).
 int encode_video_streamed(ie_ctx* c, const std::string& path, const FileParams& p, std::vector<uint8_t>& out,
                           std::string& err) {
     if (!c) return (err = "no GPU context", IE_EHIP);
@@ -148,8 +151,8 @@ int encode_video_streamed(ie_ctx* c, const std::string& path, const FileParams& 
     FILE* f = std::fopen(path.c_str(), "rb");
     if (!f) return (err = "Could not read file '" + path + "'", IE_EINVAL);
     ie_vstream* v = nullptr;
-    if ((r = ie_vstream_open(c, p.w, p.h, size_t(p.w), p.frame_pitch, p.rle ? 1 : 0, p.mode, hdr.get_buffer(), H,
-                             p.frames, &v))) {
+    if ((r = ie_vstream_open_gop(c, p.w, p.h, size_t(p.w), p.frame_pitch, p.gop, p.merange, p.rle ? 1 : 0, p.mode,
+                                 hdr.get_buffer(), H, p.frames, &v))) {
         std::fclose(f);
         return (err = ie_last_error(c), r);
     }
@@ -163,7 +166,10 @@ int encode_video_streamed(ie_ctx* c, const std::string& path, const FileParams& 
         r = ie_host_alloc(c, size_t(K) * p.frame_pitch, &b);
         buf[i] = static_cast<uint8_t*>(b);
     }
-    if (!p.huffman) out.assign(ie_stream_bound(p.w, p.h, p.n, p.frames, H), 0);
+    if (!p.huffman)
+        out.assign(p.gop > 1 ? ie_gop_stream_bound(p.w, p.h, p.n, p.frames, p.merange, H)
+                             : ie_stream_bound(p.w, p.h, p.n, p.frames, H),
+                   0);
     size_t got = 0, nb = 0;
     auto read_chunk = [&](int i, int nf) {
         return std::fread(buf[i], p.frame_pitch, size_t(nf), f) == size_t(nf);
@@ -495,13 +501,6 @@ bool VideoEncoder::process() {
     p.gop = gop;
     p.merange = merange;
     p.frame_pitch = pitch;
-    if (gop != 1) {
-        // P-frames chain through the previous frame's reconstruction: the whole video goes to the
-        // device first (as VideoBase.cpp:6-19 reads it), then one ie_encode_gop
-        std::vector<uint8_t> all;
-        if (!read_file(source_file, all)) return (err_ = "Could not read file '" + source_file + "'", false);
-        return encode_file(Device::get(), all.data(), p, result_, err_) == IE_OK;
-    }
     return encode_video_streamed(Device::get(), source_file, p, result_, err_) == IE_OK;
 }
 

@@ -205,10 +205,10 @@ size_t ie_gop_stream_bound(int w, int h, int n, int nframes, int merange, uint64
 
 }  // extern "C"
 
-namespace {
+namespace iec {
 
-// What ie_encode_gop and ie_encode_gop_groups check before any device work, in this order; gop is
-// already >= 1.  *need: ie_gop_stream_bound of the call.
+// What ie_encode_gop, ie_encode_gop_groups and ie_vstream_open_gop check before any device work, in
+// this order; gop is already >= 1.  *need: ie_gop_stream_bound of the call.
 int check_gop(ie_ctx* c, int w, int h, size_t stride, size_t frame_pitch, int nframes, int gop, int merange,
               size_t out_cap, uint64_t start_bit, size_t* need) {
     int r = check_dims(c, w, h, nframes);  // (reported before a bad merange; check_frames passes it again)
@@ -223,6 +223,128 @@ int check_gop(ie_ctx* c, int w, int h, size_t stride, size_t frame_pitch, int nf
     if (out_cap < *need) return fail(c, IE_ECAP, "output capacity below ie_gop_stream_bound");
     return IE_OK;
 }
+
+static size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
+
+// Scratch per group: the slot, two reconstructed frames, the prediction error's coefficients
+// (4x4 only) and record lengths, the tile sums, and its column of the position table.
+static void gop_wave_sizes(int n, int w, int h, int gop, int merange, GopWave* W) {
+    const int nb = (w / n) * (h / n);
+    W->gop = gop;
+    W->sz_slot = align256(ie_gop_stream_bound(w, h, n, gop, merange, 0));
+    W->sz_rec = align256(2 * size_t(w) * h);
+    W->sz_coef = n == 4 ? align256(size_t(nb) * 16 * sizeof(int16_t)) : 0;
+    W->sz_bits = align256(size_t(nb) * sizeof(uint32_t));
+    W->sz_tile = align256((size_t(ie::pframe_tiles(nb)) + 1) * sizeof(uint64_t));
+}
+
+size_t gop_wave_groups(int n, int w, int h, int gop, int merange, size_t want) {
+    GopWave W;
+    gop_wave_sizes(n, w, h, gop, merange, &W);
+    const size_t per_group = W.sz_slot + W.sz_rec + W.sz_coef + W.sz_bits + W.sz_tile + (size_t(gop) + 2) * sizeof(uint64_t);
+    size_t Gw = std::min<size_t>({std::max<size_t>(want, 1), 65535, std::max<size_t>(1, ((size_t(1) << 30) - 1024) / per_group)});
+    if (const char* eb = getenv("IE_GOP_BATCH_MAX"))  // (read on every call: a limit in groups, only ever lower)
+        if (atoll(eb) > 0) Gw = std::min<size_t>(Gw, size_t(atoll(eb)));
+    return Gw;
+}
+
+int gop_wave_scratch(ie_ctx* c, int w, int h, int gop, int merange, size_t Gw, GopWave* W) {
+    gop_wave_sizes(c->n, w, h, gop, merange, W);
+    W->Gw = Gw;
+    const size_t sz_pos = align256((size_t(gop) + 1) * Gw * sizeof(uint64_t));
+    const size_t sz_goff = align256((Gw + 1) * sizeof(uint64_t));
+    int r = ensure(c, c->d_gopg, c->cap_gopg,
+                   Gw * (W->sz_slot + W->sz_rec + W->sz_coef + W->sz_bits + W->sz_tile) + sz_pos + sz_goff);
+    if (r) return r;
+    uint8_t* p = c->d_gopg;
+    auto carve = [&p](size_t bytes) {
+        uint8_t* q = p;
+        p += bytes;
+        return q;
+    };
+    W->slots = reinterpret_cast<uint32_t*>(carve(Gw * W->sz_slot));
+    W->rec = carve(Gw * W->sz_rec);
+    W->coef = reinterpret_cast<int16_t*>(carve(Gw * W->sz_coef));
+    W->bits = reinterpret_cast<uint32_t*>(carve(Gw * W->sz_bits));
+    W->tile = reinterpret_cast<uint64_t*>(carve(Gw * W->sz_tile));
+    W->pos = reinterpret_cast<uint64_t*>(carve(sz_pos));  // [gop + 1][groups of the wave]
+    W->goff = reinterpret_cast<uint64_t*>(carve(sz_goff));
+    return IE_OK;
+}
+
+int launch_gop_wave(ie_ctx* c, const GopWave& W, const uint8_t* wy, int w, int h, size_t stride, size_t frame_pitch,
+                    int gw, int nfw, int merange, int use_rle, int mode, uint32_t* dout, uint64_t start_bit,
+                    const uint64_t* base_dev, uint64_t* fpos) {
+    const int n = c->n, gop = W.gop, bx = w / n;
+    const size_t fpx = size_t(w) * h, group_pitch = size_t(gop) * frame_pitch;
+    int r;
+    HIPCHK(c, hipMemsetAsync(W.slots, 0, size_t(gw) * W.sz_slot, c->stream));
+    HIPCHK(c, hipMemsetAsync(W.pos, 0, size_t(gw) * sizeof(uint64_t), c->stream));  // every slot starts at bit 0
+    {  // step 0: the I-frames, a batch of independent images; their end bits are pos[1][g]
+        Launch L(wy, w, h, stride, group_pitch, gw, use_rle, mode, W.slots, 0);
+        L.segmented = 1;
+        L.out_pitch = W.sz_slot;
+        L.chain_end = W.pos + gw;
+        if ((r = launch_chain(c, L))) return r;
+    }
+    for (int j = 1; j < gop && j < nfw; j++) {  // step j: frame j of the groups that have one
+        ie::PfArgs a{};
+        a.cur = wy + size_t(j) * frame_pitch;
+        a.cs = stride;
+        a.g_cur = group_pitch;
+        if (j == 1) {  // the I-frame as the caller holds it
+            a.ref = wy;
+            a.rs = stride;
+            a.g_ref = group_pitch;
+        } else {       // the previous P-frame's reconstruction
+            a.ref = W.rec + size_t((j - 1) & 1) * fpx;
+            a.rs = size_t(w);
+            a.g_ref = W.sz_rec;
+        }
+        a.rec = W.rec + size_t(j & 1) * fpx;
+        a.g_rec = W.sz_rec;
+        a.w = w;
+        a.h = h;
+        a.mbx = w / 16;
+        a.mby = h / 16;
+        a.bx = bx;
+        a.rle = use_rle ? 1 : 0;
+        a.merange = merange;
+        a.mv_bits = mvec_bits(merange);
+        a.tab = c->d_tab;
+        a.coef = W.coef;
+        a.g_coef = W.sz_coef / sizeof(int16_t);
+        a.bits = W.bits;
+        a.g_bits = W.sz_bits / sizeof(uint32_t);
+        a.g_tile = W.sz_tile / sizeof(uint64_t);
+        a.out = W.slots;
+        a.g_out = W.sz_slot / sizeof(uint32_t);
+        a.start = W.pos + size_t(j) * gw;
+        a.end = W.pos + size_t(j + 1) * gw;
+        const int gj = std::min(gw, (nfw - j + gop - 1) / gop);
+        ie::launch_pframe_groups(a, n, gj, W.tile, c->stream);
+        HIPCHK(c, hipGetLastError());
+    }
+    ie::GopSplice sp{};
+    sp.pos = W.pos;
+    sp.groups = gw;
+    sp.gop = gop;
+    sp.nframes = nfw;
+    sp.slots = W.slots;
+    sp.slot_words = W.sz_slot / sizeof(uint32_t);
+    sp.out = dout;
+    sp.base = start_bit;
+    sp.base_dev = base_dev;
+    sp.goff = W.goff;
+    sp.fpos = fpos;
+    ie::launch_gop_splice(sp, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return IE_OK;
+}
+
+}  // namespace iec
+
+namespace {
 
 // Where the P-frame payload is built: the caller's device stream, or zeroed staging (the P-frame
 // records are ORed in) holding the caller's leading bytes.  Word 0 of *dout = stream bytes [0, 4).
@@ -265,8 +387,6 @@ int clear_gop_stream(ie_ctx* c, uint8_t* out, uint64_t start_bit, size_t need) {
     if (b1 > b0 && (r = lead_bits(false))) return r;
     return IE_OK;
 }
-
-size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 }  // namespace
 
@@ -390,106 +510,20 @@ int ie_encode_gop_groups(ie_ctx* c, const uint8_t* y, int w, int h, size_t strid
     uint32_t* dout;
     if ((r = stage_gop_out(c, out, out_dev, need, start_bit, &dout))) return r;
 
-    // Scratch per group: the slot, two reconstructed frames, the prediction error's coefficients
-    // (4x4 only) and record lengths, the tile sums, and its column of the position table; a video
-    // that would need more than 1 GiB (or 65535 groups: grid.y) runs as waves of groups that share
-    // the scratch in stream order (IE_GOP_BATCH_MAX, read on every call, lowers their size further).
-    const int n = c->n, bx = w / n, nb = bx * (h / n), G = (nframes + gop - 1) / gop;
-    const size_t fpx = size_t(w) * h;
-    const size_t sz_slot = align256(ie_gop_stream_bound(w, h, n, gop, merange, 0)), sz_rec = align256(2 * fpx);
-    const size_t sz_coef = n == 4 ? align256(size_t(nb) * 16 * sizeof(int16_t)) : 0;
-    const size_t sz_bits = align256(size_t(nb) * sizeof(uint32_t));
-    const size_t sz_tile = align256((size_t(ie::pframe_tiles(nb)) + 1) * sizeof(uint64_t));
-    const size_t per_group = sz_slot + sz_rec + sz_coef + sz_bits + sz_tile + (size_t(gop) + 2) * sizeof(uint64_t);
-    size_t Gw = std::min<size_t>({size_t(G), 65535, std::max<size_t>(1, ((size_t(1) << 30) - 1024) / per_group)});
-    if (const char* eb = getenv("IE_GOP_BATCH_MAX"))  // (read on every call: a limit in groups, only ever lower)
-        if (atoll(eb) > 0) Gw = std::min<size_t>(Gw, size_t(atoll(eb)));
-    const size_t sz_pos = align256((size_t(gop) + 1) * Gw * sizeof(uint64_t));
-    const size_t sz_goff = align256((Gw + 1) * sizeof(uint64_t));
-    if ((r = ensure(c, c->d_gopg, c->cap_gopg, Gw * (per_group - (size_t(gop) + 2) * sizeof(uint64_t)) + sz_pos + sz_goff)))
-        return r;
-    uint8_t* p = c->d_gopg;
-    auto carve = [&p](size_t bytes) {
-        uint8_t* q = p;
-        p += bytes;
-        return q;
-    };
-    uint32_t* const slots = reinterpret_cast<uint32_t*>(carve(Gw * sz_slot));
-    uint8_t* const rec = carve(Gw * sz_rec);
-    int16_t* const coef = reinterpret_cast<int16_t*>(carve(Gw * sz_coef));
-    uint32_t* const bits = reinterpret_cast<uint32_t*>(carve(Gw * sz_bits));
-    uint64_t* const tile = reinterpret_cast<uint64_t*>(carve(Gw * sz_tile));
-    uint64_t* const pos = reinterpret_cast<uint64_t*>(carve(sz_pos));  // [gop + 1][groups of the wave]
-    uint64_t* const goff = reinterpret_cast<uint64_t*>(carve(sz_goff));
+    // A video whose groups' scratch would pass 1 GiB (or 65535 groups: grid.y) runs as waves of
+    // groups that share the scratch in stream order (gop_wave_groups; IE_GOP_BATCH_MAX lowers their
+    // size further); every wave's splice starts at the previous wave's end bit, read on the device.
+    const int G = (nframes + gop - 1) / gop;
+    GopWave W;
+    if ((r = gop_wave_scratch(c, w, h, gop, merange, gop_wave_groups(c->n, w, h, gop, merange, size_t(G)), &W))) return r;
     if ((r = ensure(c, c->d_gop_pos, c->cap_gop_pos, size_t(nframes) + 1))) return r;
-
-    for (int g0 = 0; g0 < G; g0 += int(Gw)) {
-        const int gw = std::min(int(Gw), G - g0);
+    for (int g0 = 0; g0 < G; g0 += int(W.Gw)) {
+        const int gw = std::min(int(W.Gw), G - g0);
         const int f0 = g0 * gop;  // (< nframes)
         const int nfw = int(std::min<int64_t>(int64_t(nframes) - f0, int64_t(gw) * gop));
-        const uint8_t* wy = dy + size_t(f0) * frame_pitch;
-        const size_t group_pitch = size_t(gop) * frame_pitch;
-        HIPCHK(c, hipMemsetAsync(slots, 0, size_t(gw) * sz_slot, c->stream));
-        HIPCHK(c, hipMemsetAsync(pos, 0, size_t(gw) * sizeof(uint64_t), c->stream));  // every slot starts at bit 0
-        {  // step 0: the I-frames, a batch of independent images; their end bits are pos[1][g]
-            Launch L(wy, w, h, stride, group_pitch, gw, use_rle, mode, slots, 0);
-            L.segmented = 1;
-            L.out_pitch = sz_slot;
-            L.chain_end = pos + gw;
-            if ((r = launch_chain(c, L))) return r;
-        }
-        for (int j = 1; j < gop && j < nfw; j++) {  // step j: frame j of the groups that have one
-            ie::PfArgs a{};
-            a.cur = wy + size_t(j) * frame_pitch;
-            a.cs = stride;
-            a.g_cur = group_pitch;
-            if (j == 1) {  // the I-frame as the caller holds it
-                a.ref = wy;
-                a.rs = stride;
-                a.g_ref = group_pitch;
-            } else {       // the previous P-frame's reconstruction
-                a.ref = rec + size_t((j - 1) & 1) * fpx;
-                a.rs = size_t(w);
-                a.g_ref = sz_rec;
-            }
-            a.rec = rec + size_t(j & 1) * fpx;
-            a.g_rec = sz_rec;
-            a.w = w;
-            a.h = h;
-            a.mbx = w / 16;
-            a.mby = h / 16;
-            a.bx = bx;
-            a.rle = use_rle ? 1 : 0;
-            a.merange = merange;
-            a.mv_bits = mvec_bits(merange);
-            a.tab = c->d_tab;
-            a.coef = coef;
-            a.g_coef = sz_coef / sizeof(int16_t);
-            a.bits = bits;
-            a.g_bits = sz_bits / sizeof(uint32_t);
-            a.g_tile = sz_tile / sizeof(uint64_t);
-            a.out = slots;
-            a.g_out = sz_slot / sizeof(uint32_t);
-            a.start = pos + size_t(j) * gw;
-            a.end = pos + size_t(j + 1) * gw;
-            const int gj = std::min(gw, (nfw - j + gop - 1) / gop);
-            ie::launch_pframe_groups(a, n, gj, tile, c->stream);
-            HIPCHK(c, hipGetLastError());
-        }
-        ie::GopSplice sp{};
-        sp.pos = pos;
-        sp.groups = gw;
-        sp.gop = gop;
-        sp.nframes = nfw;
-        sp.slots = slots;
-        sp.slot_words = sz_slot / sizeof(uint32_t);
-        sp.out = dout;
-        sp.base = start_bit;
-        sp.base_dev = g0 ? c->d_gop_pos + f0 : nullptr;  // the previous wave's end bit
-        sp.goff = goff;
-        sp.fpos = c->d_gop_pos + f0;
-        ie::launch_gop_splice(sp, c->stream);
-        HIPCHK(c, hipGetLastError());
+        if ((r = launch_gop_wave(c, W, dy + size_t(f0) * frame_pitch, w, h, stride, frame_pitch, gw, nfw, merange, use_rle,
+                                 mode, dout, start_bit, g0 ? c->d_gop_pos + f0 : nullptr, c->d_gop_pos + f0)))
+            return r;
     }
     std::vector<uint64_t> fp(size_t(nframes) + 1);
     HIPCHK(c, hipMemcpyAsync(fp.data(), c->d_gop_pos, fp.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));

@@ -33,17 +33,29 @@ struct ie_pipe {
     uint64_t* d_ends = nullptr;    // device [2]: chained launches read the previous end here
 };
 
-// ---- streamed gop=1 video (ie_vstream_*) ----------------------------------------------------
+// ---- streamed video (ie_vstream_*) ----------------------------------------------------------
 // One bit-contiguous chain (Frame.cpp:31-45, VideoEncoder.cpp:83-91) grown chunk by chunk on the
 // device: chunk k's launch starts at chunk k-1's chain end read on the device (start_dev), so the
 // host never waits for an encode before launching the next; the finished bytes leave through the
 // D2H stream while later chunks encode.
+// With P-frames (gop > 1, ie_vstream_open_gop) a chunk is K / gop whole groups of pictures and its
+// launches are one wave of ie_encode_gop_groups (launch_gop_wave) whose splice starts at the
+// previous chunk's end bit in d_pos.  Frames gather in the current input slot across pushes until
+// it holds a chunk; finish launches what is left.  The table is the stream's own, not the
+// context's d_gop_pos: an ie_encode_gop between two pushes would overwrite the end bit the next
+// chunk starts from.  The group scratch is the context's (d_gopg): it is live only inside one
+// chunk's launches, all enqueued by one call in stream order.
 struct ie_vstream {
     ie_ctx* c = nullptr;
     int w = 0, h = 0, rle = 1, mode = IE_MODE_FAST;
+    int gop = 1, merange = 0;
+    int fill = 0;                    // gop > 1: frames in the current input slot, not launched yet
+    uint64_t* d_pos = nullptr;       // gop > 1: device [max_frames + 1] first bit of every launched frame; a
+                                     // chunk's end bit lies where the next chunk's first frame goes
+    uint64_t* h_pos = nullptr;       // gop > 1: pinned [2][K + 1] read-back of a chunk's part of d_pos
     size_t stride = 0, frame_pitch = 0;
     uint64_t start_bit = 0;
-    int max_frames = 0, frames = 0;  // capacity, frames pushed
+    int max_frames = 0, frames = 0;  // capacity, frames launched
     int K = 1;                       // frames per chunk
     uint8_t* d_stream = nullptr;     // the whole stream from byte 0 (the caller's head included)
     size_t cap = 0;
@@ -132,27 +144,29 @@ int slot_pinned(ie_ctx* c, uint8_t*& p, size_t& cap, size_t need) {
 
 // frames per chunk: ~8 MiB of pixels (at least 1, at most kMaxChunk), and at least two chunks
 // (IE_CHUNK_MB overrides the target: a tuning aid, the output does not depend on it)
-int chunk_frames(size_t frame_bytes, int nframes) {
+size_t chunk_target() {
     const char* e = getenv("IE_CHUNK_MB");
-    const size_t target = (e && atof(e) > 0) ? size_t(atof(e) * 1048576.0) : size_t(8) << 20;
-    int k = int(std::max<size_t>(1, target / std::max<size_t>(1, frame_bytes)));
+    return (e && atof(e) > 0) ? size_t(atof(e) * 1048576.0) : size_t(8) << 20;
+}
+int chunk_frames(size_t frame_bytes, int nframes) {
+    int k = int(std::max<size_t>(1, chunk_target() / std::max<size_t>(1, frame_bytes)));
     k = std::min(k, kMaxChunk);
     k = std::min(k, (nframes + 1) / 2);
     return std::max(k, 1);
 }
 
-// Upload chunk `k` (frames f0 .. f0+nf-1) into device slot s on the H2D stream.
+// Upload chunk `k` (frames f0 .. f0+nf-1) into device slot s, from byte `at` of it on, on the H2D stream.
 int pipe_upload(ie_ctx* c, Pipe* P, int s, const uint8_t* y, size_t frame_pitch, size_t in_bytes, int f0,
-                bool pinned_in) {
+                bool pinned_in, size_t at = 0) {
     // d_in[s] is free once the encode of the chunk that last used it is done
     if (P->rec_enc[s]) HIPCHK(c, hipStreamWaitEvent(P->h2d, P->ev_enc[s], 0));
     const uint8_t* src = y + size_t(f0) * frame_pitch;
     if (pinned_in) {
-        HIPCHK(c, hipMemcpyAsync(P->d_in[s], src, in_bytes, hipMemcpyHostToDevice, P->h2d));
+        HIPCHK(c, hipMemcpyAsync(P->d_in[s] + at, src, in_bytes, hipMemcpyHostToDevice, P->h2d));
     } else {
         if (P->rec_h2d[s]) HIPCHK(c, hipEventSynchronize(P->ev_h2d[s]));  // h_in[s] drained
-        par_copy(P->h_in[s], src, in_bytes);
-        HIPCHK(c, hipMemcpyAsync(P->d_in[s], P->h_in[s], in_bytes, hipMemcpyHostToDevice, P->h2d));
+        par_copy(P->h_in[s] + at, src, in_bytes);
+        HIPCHK(c, hipMemcpyAsync(P->d_in[s] + at, P->h_in[s] + at, in_bytes, hipMemcpyHostToDevice, P->h2d));
     }
     HIPCHK(c, hipEventRecord(P->ev_h2d[s], P->h2d));
     P->rec_h2d[s] = true;
@@ -165,9 +179,9 @@ int vs_harvest(ie_vstream* v) {
     Pipe* P = v->P;
     const int j = v->harvested, s = j & 1;
     HIPCHK(c, hipEventSynchronize(P->ev_enc[s]));
-    const uint64_t* hs = P->h_ends + s * (kMaxChunk + 1);
+    const uint64_t* hs = v->gop > 1 ? v->h_pos + size_t(s) * size_t(v->K + 1) : P->h_ends + s * (kMaxChunk + 1);
     for (int i = 0; i < v->chunk_nf[s]; i++) v->fs[size_t(v->chunk_f0[s] + i)] = hs[i];
-    v->done_bits = hs[kMaxChunk];
+    v->done_bits = hs[v->gop > 1 ? v->chunk_nf[s] : kMaxChunk];
     v->harvested = j + 1;
     return IE_OK;
 }
@@ -200,6 +214,49 @@ int vs_chunk(ie_vstream* v, const uint8_t* frames, int nf, bool pinned_in) {
     v->chunk_nf[s] = nf;
     v->frames += nf;
     v->chunks = k + 1;
+    return IE_OK;
+}
+
+// gop > 1: launch the v->fill frames gathered in the current input slot as one wave of groups.
+int vs_gop_launch(ie_vstream* v) {
+    ie_ctx* c = v->c;
+    Pipe* P = v->P;
+    const int k = v->chunks, s = k & 1, nfw = v->fill, gw = (nfw + v->gop - 1) / v->gop;
+    int r;
+    while (k - v->harvested >= 2)  // slot s's read-back area still holds chunk k-2's positions
+        if ((r = vs_harvest(v))) return r;
+    HIPCHK(c, hipStreamWaitEvent(c->stream, P->ev_h2d[s], 0));
+    // (carved on every chunk: a call between two pushes may have grown the context's scratch)
+    GopWave W;
+    if ((r = gop_wave_scratch(c, v->w, v->h, v->gop, v->merange, size_t(v->K / v->gop), &W))) return r;
+    uint64_t* fpos = v->d_pos + v->frames;  // fpos[0] holds the previous chunk's end bit
+    if ((r = launch_gop_wave(c, W, P->d_in[s], v->w, v->h, v->stride, v->frame_pitch, gw, nfw, v->merange, v->rle, v->mode,
+                             reinterpret_cast<uint32_t*>(v->d_stream), v->start_bit, k ? fpos : nullptr, fpos)))
+        return r;
+    HIPCHK(c, hipMemcpyAsync(v->h_pos + size_t(s) * size_t(v->K + 1), fpos, size_t(nfw + 1) * sizeof(uint64_t),
+                             hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(P->ev_enc[s], c->stream));
+    P->rec_enc[s] = true;
+    note_async(c, "streamed video encode");
+    v->chunk_f0[s] = v->frames;
+    v->chunk_nf[s] = nfw;
+    v->frames += nfw;
+    v->fill = 0;
+    v->chunks = k + 1;
+    return IE_OK;
+}
+
+// gop > 1: frames go to the current input slot behind those already there; a full slot is launched.
+int vs_gop_push(ie_vstream* v, const uint8_t* frames, int nframes, bool pinned_in) {
+    for (int f = 0; f < nframes;) {
+        const int s = v->chunks & 1, nf = std::min(v->K - v->fill, nframes - f);
+        int r = pipe_upload(v->c, v->P, s, frames, v->frame_pitch, frames_span(nf, v->frame_pitch, v->stride, v->w, v->h),
+                            f, pinned_in, size_t(v->fill) * v->frame_pitch);
+        if (r) return r;
+        v->fill += nf;
+        f += nf;
+        if (v->fill == v->K && (r = vs_gop_launch(v))) return r;
+    }
     return IE_OK;
 }
 
@@ -240,23 +297,30 @@ int vs_copy_out(ie_vstream* v, uint8_t* dst, uint64_t b1) {
     return IE_OK;
 }
 
-}  // namespace
+void vs_free(ie_vstream* v) {
+    pipe_free(v->P);
+    (void)hipFree(v->d_stream);
+    (void)hipFree(v->d_pos);
+    if (v->h_pos) (void)hipHostFree(v->h_pos);
+    delete v;
+}
 
-extern "C" {
-
-int ie_vstream_open(ie_ctx* c, int w, int h, size_t stride, size_t frame_pitch, int use_rle, int mode,
-                    const uint8_t* head, uint64_t start_bit, int max_frames, ie_vstream** out) {
+// ie_vstream_open (gop = 1) and ie_vstream_open_gop (gop > 1)
+int vs_open(ie_ctx* c, int w, int h, size_t stride, size_t frame_pitch, int gop, int merange, int use_rle, int mode,
+            const uint8_t* head, uint64_t start_bit, int max_frames, ie_vstream** out) {
     if (!c || !out || max_frames <= 0 || (start_bit && !head)) return IE_EINVAL;
     *out = nullptr;
     // (frames arrive push by push: the pitch must hold a frame even when max_frames is 1)
     int r = check_frames(c, w, h, std::max(max_frames, 2), stride, frame_pitch);
     if (r) return r;
+    size_t gop_cap = 0;
+    if (gop > 1 && (r = check_gop(c, w, h, stride, frame_pitch, max_frames, gop, merange, SIZE_MAX, start_bit, &gop_cap)))
+        return r;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     ie_vstream* v = new ie_vstream();
     if ((r = pipe_new(c, v->P))) {
-        pipe_free(v->P);
-        delete v;
+        vs_free(v);
         return r;
     }
     Pipe* P = v->P;
@@ -269,29 +333,41 @@ int ie_vstream_open(ie_ctx* c, int w, int h, size_t stride, size_t frame_pitch, 
     v->mode = mode;
     v->start_bit = start_bit;
     v->max_frames = max_frames;
-    v->K = chunk_frames(stride * size_t(h), 1 << 20);
+    v->gop = std::max(gop, 1);
+    v->merange = merange;
+    if (gop > 1) {
+        // a chunk is Gc whole groups: IE_CHUNK_MB's pixel target (no more than the video has), under
+        // the ceilings of a wave of ie_encode_gop_groups (gop_wave_groups), at least one group
+        const size_t G = (size_t(max_frames) + size_t(gop) - 1) / size_t(gop);
+        const size_t want = std::min(G, chunk_target() / std::max<size_t>(1, stride * size_t(h) * size_t(gop)));
+        v->K = int(gop_wave_groups(c->n, w, h, gop, merange, want)) * gop;
+    } else {
+        v->K = chunk_frames(stride * size_t(h), 1 << 20);
+    }
     v->fs.assign(size_t(max_frames), 0);
     v->done_bits = start_bit;
-    v->cap = ie_stream_bound(w, h, c->n, max_frames, start_bit);
+    v->cap = gop > 1 ? gop_cap : ie_stream_bound(w, h, c->n, max_frames, start_bit);
     const size_t in_bytes = frames_span(v->K, frame_pitch, stride, w, h);
     auto bad = [&](int code) {
-        (void)hipFree(v->d_stream);
-        pipe_free(v->P);
-        delete v;
+        vs_free(v);
         return code;
     };
     if (hipMalloc(&v->d_stream, v->cap) != hipSuccess) return bad(fail(c, IE_EHIP, "hipMalloc(video stream)"));
+    if (gop > 1 && (hipMalloc(&v->d_pos, (size_t(max_frames) + 1) * sizeof(uint64_t)) != hipSuccess ||
+                    hipHostMalloc(&v->h_pos, 2 * size_t(v->K + 1) * sizeof(uint64_t)) != hipSuccess))
+        return bad(fail(c, IE_EHIP, "hipMalloc(video stream positions)"));
     for (int s = 0; s < 2; s++) {
         if ((r = slot_dev(c, P->d_in[s], P->cap_din[s], in_bytes))) return bad(r);
         if ((r = slot_pinned(c, P->h_in[s], P->cap_hin[s], in_bytes))) return bad(r);
     }
     // the caller's head: bytes [0, ceil(start_bit/8)), bits from start_bit on cleared; the word
-    // holding start_bit is completed by the first chunk's first tile
+    // holding start_bit is completed by the first chunk's first tile.  gop > 1: the splice ORs every
+    // group's first and last word into the stream, so all of it starts as zeros.
     const size_t hb = size_t((start_bit + 7) / 8);
     std::vector<uint8_t> hd(hb + 8, 0);
     if (hb) std::memcpy(hd.data(), head, hb);
     if (start_bit % 8) hd[hb - 1] &= uint8_t(0xFF00u >> (start_bit % 8));
-    if (hipMemsetAsync(v->d_stream, 0, std::min(v->cap, hb + 8), c->stream) != hipSuccess ||
+    if (hipMemsetAsync(v->d_stream, 0, gop > 1 ? v->cap : std::min(v->cap, hb + 8), c->stream) != hipSuccess ||
         (hb && hipMemcpyAsync(v->d_stream, hd.data(), hb, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
         hipStreamSynchronize(c->stream) != hipSuccess)
         return bad(fail(c, IE_EHIP, "video stream head upload"));
@@ -299,16 +375,33 @@ int ie_vstream_open(ie_ctx* c, int w, int h, size_t stride, size_t frame_pitch, 
     return IE_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int ie_vstream_open(ie_ctx* c, int w, int h, size_t stride, size_t frame_pitch, int use_rle, int mode,
+                    const uint8_t* head, uint64_t start_bit, int max_frames, ie_vstream** out) {
+    return vs_open(c, w, h, stride, frame_pitch, 1, 0, use_rle, mode, head, start_bit, max_frames, out);
+}
+
+int ie_vstream_open_gop(ie_ctx* c, int w, int h, size_t stride, size_t frame_pitch, int gop, int merange, int use_rle,
+                        int mode, const uint8_t* head, uint64_t start_bit, int max_frames, ie_vstream** out) {
+    if (gop <= 1)
+        return ie_vstream_open(c, w, h, stride, frame_pitch, use_rle, mode, head, start_bit, max_frames, out);
+    return vs_open(c, w, h, stride, frame_pitch, gop, merange, use_rle, mode, head, start_bit, max_frames, out);
+}
+
 int ie_vstream_push(ie_vstream* v, const uint8_t* frames, int nframes) {
     if (!v || (!frames && nframes)) return IE_EINVAL;
     ie_ctx* c = v->c;
-    if (nframes < 0 || v->frames + nframes > v->max_frames)
+    if (nframes < 0 || v->frames + v->fill + nframes > v->max_frames)
         return fail(c, IE_ECAP, "more frames pushed than ie_vstream_open's max_frames");
     if (ie_is_device_ptr(frames)) return fail(c, IE_EINVAL, "ie_vstream_push takes host frames");
     HIPCHK(c, hipSetDevice(c->device));
     // the previous push's pinned frames may still be in flight: they are released now
     HIPCHK(c, hipStreamSynchronize(v->P->h2d));
     const bool pinned = is_pinned_ptr(frames);
+    if (v->gop > 1) return vs_gop_push(v, frames, nframes, pinned);
     for (int f = 0; f < nframes; f += v->K) {
         const int r = vs_chunk(v, frames + size_t(f) * v->frame_pitch, std::min(v->K, nframes - f), pinned);
         if (r) return r;
@@ -340,6 +433,7 @@ int ie_vstream_finish(ie_vstream* v, uint8_t* dst, size_t cap, size_t* nbytes, u
     ie_ctx* c = v->c;
     if (nbytes) *nbytes = 0;
     int r;
+    if (v->fill && (r = vs_gop_launch(v))) return r;  // gop > 1: the remainder, its last group maybe short
     while (v->harvested < v->chunks)
         if ((r = vs_harvest(v))) return r;
     unsigned timeouts = 0;
@@ -365,9 +459,7 @@ int ie_vstream_close(ie_vstream* v) {
     if (!v) return IE_OK;
     ie_ctx* c = v->c;
     (void)hipStreamSynchronize(c->stream);
-    pipe_free(v->P);
-    (void)hipFree(v->d_stream);
-    delete v;
+    vs_free(v);
     return IE_OK;
 }
 

@@ -324,6 +324,35 @@ int encode(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t fram
            int use_rle, int mode, uint8_t* out, size_t out_cap, size_t out_pitch, uint64_t start_bit,
            int segmented, uint64_t* frame_bits, uint64_t* end_bits, int16_t* coef = nullptr,
            uint32_t* hist = nullptr);
+// What every P-frame entry point checks before any device work (gop already >= 1); *need:
+// ie_gop_stream_bound of the call, IE_ECAP when out_cap is below it.
+int check_gop(ie_ctx* c, int w, int h, size_t stride, size_t frame_pitch, int nframes, int gop, int merange,
+              size_t out_cap, uint64_t start_bit, size_t* need);
+// One wave of groups of pictures encoded side by side (ie_encode_gop_groups; a chunk of a gop > 1
+// ie_vstream): the context's group scratch (d_gopg) carved for up to Gw groups.
+struct GopWave {
+    int gop = 0;
+    size_t Gw = 0;  // groups the scratch holds
+    size_t sz_slot = 0, sz_rec = 0, sz_coef = 0, sz_bits = 0, sz_tile = 0;  // bytes per group
+    uint32_t* slots = nullptr;
+    uint8_t* rec = nullptr;
+    int16_t* coef = nullptr;
+    uint32_t* bits = nullptr;
+    uint64_t *tile = nullptr, *pos = nullptr, *goff = nullptr;
+};
+// Groups per wave: `want`, at most 65535 (grid.y), at most what keeps the scratch under 1 GiB, at
+// most IE_GOP_BATCH_MAX (read on every call), at least 1.
+size_t gop_wave_groups(int n, int w, int h, int gop, int merange, size_t want);
+// Grows d_gopg if it must and carves it.  The pointers hold until another call grows it: carve
+// again before every run of launches.
+int gop_wave_scratch(ie_ctx* c, int w, int h, int gop, int merange, size_t Gw, GopWave* W);
+// The launches of one wave over device frames wy (gw <= W.Gw groups, nfw frames, only the last
+// group may be short), no synchronisation: zero the slots, the I-frames as a batch of independent
+// images, steps 1 .. gop-1 of the P-frames, the splice into dout from *base_dev (null: start_bit).
+// fpos[0 .. nfw] receives the frames' first bits in dout and the wave's end bit.
+int launch_gop_wave(ie_ctx* c, const GopWave& W, const uint8_t* wy, int w, int h, size_t stride, size_t frame_pitch,
+                    int gw, int nfw, int merange, int use_rle, int mode, uint32_t* dout, uint64_t start_bit,
+                    const uint64_t* base_dev, uint64_t* fpos);
 
 // ---- ie_capi_stream.cpp: host frames in, host streams out
 int streamed_images(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,

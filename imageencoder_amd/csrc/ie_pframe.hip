@@ -489,6 +489,9 @@ __global__ __launch_bounds__(kTPB) void gop_splice_kernel(GopSplice a) {
     for (uint64_t i = uint64_t(blockIdx.x) * kTPB + threadIdx.x; i < nw; i += uint64_t(gridDim.x) * kTPB) {
         const uint32_t hi = i ? bswap32(src[i - 1]) : 0u;
         const uint32_t v = bswap32(__builtin_amdgcn_alignbit(hi, bswap32(src[i]), sh));
+        // (v's bits before the group's first bit are zero: the OR only adds bits behind the previous
+        // group's -- or, in a streamed video, the previous chunk's -- last bit, so whole bytes of
+        // this word that ie_vstream_pull already handed out keep their values)
         if (i == 0 || i == nw - 1) atomicOr(dst + i, v);
         else dst[i] = v;
     }

@@ -188,7 +188,7 @@ int ie_is_device_ptr(const void* p);
 int ie_host_alloc(ie_ctx* ctx, size_t bytes, void** out);
 int ie_host_free(ie_ctx* ctx, void* p);
 
-/* Streamed gop=1 video payload (Frame.cpp:31-45 / VideoEncoder.cpp:83-91 for frames that arrive
+/* Streamed video payload, gop=1 (Frame.cpp:31-45 / VideoEncoder.cpp:83-91 for frames that arrive
  * over time, e.g. read from a .raw/YUV420 file chunk by chunk): ONE bit-contiguous stream grown on
  * the device.  open: `head` holds the caller's bytes [0, ceil(start_bit/8)) (the settings header;
  * bits from start_bit on are ignored), max_frames bounds the device stream.  push: host frames
@@ -201,10 +201,31 @@ int ie_host_free(ie_ctx* ctx, void* p);
  * error counters, copies the remaining bytes (last byte zero-padded) to dst when dst != NULL, and
  * returns the end bit and optionally each frame's payload bits.  ie_vstream_device: the device
  * stream (valid until close; complete after finish), e.g. for the device Huffman pass.  One open
- * stream per context at a time; other calls on the context between pushes are allowed. */
+ * stream per context at a time; other calls on the context between pushes are allowed.
+ *
+ * ie_vstream_open_gop: the same stream for a video with P-frames (gop > 1; with gop <= 1 the call
+ * is ie_vstream_open).  push, pull, finish, device and close serve both kinds with the contract
+ * above.  For ANY partition of the video's frames into pushes, the bytes (all pulls, then finish's
+ * copy; also the device stream after finish), *end_bit and frame_bits[] equal ie_encode_gop's on
+ * the whole video with the same start_bit and the same bits before it.  Checks: ie_vstream_open's,
+ * then ie_encode_gop's with the same codes (merange in [0, 32767]; IE_EINVAL for P-frames with
+ * W % 16 != 0 and H >= 32).  The device stream holds ie_gop_stream_bound(w, h, n, max_frames,
+ * merange, start_bit) bytes, zeroed from the head on at open.  A chunk is Gc whole groups of
+ * pictures (Gc * gop frames): frames gather across pushes in one of two device input slots (pushes
+ * need not align with groups), a full slot is encoded as one wave of ie_encode_gop_groups whose
+ * splice starts at the previous chunk's end bit read on the device, and finish encodes what is
+ * left (its last group may be short).  Gc: IE_CHUNK_MB's pixel target (default 8 MiB), at most a
+ * wave of ie_encode_gop_groups (1 GiB of scratch, 65535 groups, IE_GOP_BATCH_MAX), at least 1; all
+ * read at open, none changes the output.  pull hands out the whole bytes up to the end of the
+ * last finished chunk; a later chunk only adds bits to a byte that is not whole yet.  A look-back
+ * timeout makes finish return IE_EDEVICE: earlier chunks' frames are gone, nothing is redone.  The
+ * stream keeps its own table of frame positions, so an ie_encode_gop between pushes is harmless. */
 typedef struct ie_vstream ie_vstream;
 int ie_vstream_open(ie_ctx* ctx, int w, int h, size_t stride, size_t frame_pitch, int use_rle, int mode,
                     const uint8_t* head, uint64_t start_bit, int max_frames, ie_vstream** out);
+int ie_vstream_open_gop(ie_ctx* ctx, int w, int h, size_t stride, size_t frame_pitch, int gop, int merange,
+                        int use_rle, int mode, const uint8_t* head, uint64_t start_bit, int max_frames,
+                        ie_vstream** out);
 int ie_vstream_push(ie_vstream* v, const uint8_t* frames, int nframes);
 int ie_vstream_pull(ie_vstream* v, uint8_t* dst, size_t cap, size_t* nbytes);
 int ie_vstream_finish(ie_vstream* v, uint8_t* dst, size_t cap, size_t* nbytes, uint64_t* end_bit,

@@ -246,10 +246,11 @@ private:
 };
 
 // dc::VideoProcessor (VideoBase.hpp:17-48): the video encoder / decoder base; frames are YUV420
-// (Y + W*H/2 bytes, VideoBase.cpp:6-19).  gop = 1 only: every frame an I-frame, payloads
-// concatenated bit-contiguously after a 210-bit header (VideoEncoder.cpp:22-107, Frame.cpp:31-45).
-// gop > 1 needs motion estimation (P-frames), outside this library's scope: process() then fails
-// with an explanatory error.
+// (Y + W*H/2 bytes, VideoBase.cpp:6-19).  The payloads follow a 210-bit header bit-contiguously
+// (VideoEncoder.cpp:22-107, Frame.cpp:31-45).  Any gop: frame f is an I-frame when f % gop == 0,
+// every other frame a P-frame (motion search + coded prediction error).  The encoder streams the
+// file through an ie_vstream for every gop (with gop > 1 in chunks of whole groups of pictures,
+// ie_vstream_open_gop) and never holds the whole video; the decoder reads the file whole.
 class VideoProcessor {
 public:
     VideoProcessor(const std::string& source_file, const std::string& dest_file, const uint16_t& width,
@@ -333,7 +334,7 @@ int64_t ieh_encode_image(ie_ctx* ctx, const uint8_t* y, int w, int h, const uint
 int64_t ieh_encode_video(ie_ctx* ctx, const uint8_t* yuv, size_t len, int w, int h, const uint16_t* q, int n,
                          int rle, int huffman, int merange, int mode, uint8_t* out, size_t cap);
 // Video file with I/P-frames: frame f is an I-frame when f % gop == 0 (VideoEncoder.cpp:22-107; the
-// P-frames' motion search + coded error through ie_encode_gop).  gop = 1: ieh_encode_video.
+// P-frames' motion search + coded error through ie_encode_gop_groups).  gop = 1: ieh_encode_video.
 int64_t ieh_encode_video_gop(ie_ctx* ctx, const uint8_t* yuv, size_t len, int w, int h, const uint16_t* q, int n,
                              int rle, int huffman, int gop, int merange, int mode, uint8_t* out, size_t cap);
 // Decode an image file (host buffer) with block size n: pixels into out (w*h bytes).  A cap
