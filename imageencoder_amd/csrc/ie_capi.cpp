@@ -8,57 +8,31 @@ using namespace iec;
 
 namespace iec {
 
-// pinned host staging (the stream is synchronised before an existing buffer is replaced)
-int ensure_pinned(ie_ctx* c, uint8_t*& p, size_t& cap, size_t need) {
-    if (cap >= need && p) return IE_OK;
-    if (p) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipHostFree(p));
-        p = nullptr;
-    }
-    const size_t n = std::max(need, cap + cap / 2);
-    HIPCHK(c, hipHostMalloc(&p, n));
-    cap = n;
-    return IE_OK;
-}
-
 int prepare_state(ie_ctx* c, int ntiles, int nframes) {
-    if (size_t(ntiles) > c->cap_tiles) {
-        if (c->d_state) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, hipFree(c->d_state));
-        }
-        const size_t cap = std::max<size_t>(ntiles, c->cap_tiles * 2);
-        HIPCHK(c, hipMalloc(&c->d_state, size_t(ie::kStateWordsPerTile) * cap * sizeof(uint64_t)));
-        if (c->d_wave_fix) HIPCHK(c, hipFree(c->d_wave_fix));
-        HIPCHK(c, hipMalloc(&c->d_wave_fix, cap * 16 * sizeof(uint32_t)));
-        HIPCHK(c, hipMemsetAsync(c->d_state, 0, size_t(ie::kStateWordsPerTile) * cap * sizeof(uint64_t), c->stream));
-        c->cap_tiles = cap;
+    int r;
+    if (size_t(ntiles) > c->state_tiles()) {
+        // the tile capacity doubles; d_wave_fix is sized from it (the stream has been waited for by then)
+        const size_t cap = std::max<size_t>(ntiles, c->state_tiles() * 2);
+        if ((r = c->d_state.reserve(c, size_t(ie::kStateWordsPerTile) * cap))) return r;
+        if ((r = c->d_wave_fix.reserve(c, cap * 16, Wait::None))) return r;
+        HIPCHK(c, hipMemsetAsync(c->d_state, 0, c->d_state.cap() * sizeof(uint64_t), c->stream));
         c->tag = 0;
     }
     c->tag++;
     if (c->tag > 255) {
-        HIPCHK(c, hipMemsetAsync(c->d_state, 0, size_t(ie::kStateWordsPerTile) * c->cap_tiles * sizeof(uint64_t), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_state, 0, c->d_state.cap() * sizeof(uint64_t), c->stream));
         c->tag = 1;
     }
-    if (size_t(nframes) > c->cap_frames) {
-        if (c->d_frame_start) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, hipFree(c->d_frame_start));
-            HIPCHK(c, hipFree(c->d_chain_end));
-        }
-        const size_t cap = std::max<size_t>(nframes, 64);
-        HIPCHK(c, hipMalloc(&c->d_frame_start, cap * sizeof(uint64_t)));
-        HIPCHK(c, hipMalloc(&c->d_chain_end, cap * sizeof(uint64_t)));
-        c->cap_frames = cap;
-    }
-    return IE_OK;
+    // at least 64 frames; the two grow together
+    const size_t frames = std::max<size_t>(nframes, 64);
+    if ((r = c->d_frame_start.reserve(c, frames))) return r;
+    return c->d_chain_end.reserve(c, frames, Wait::None);
 }
 
 // Timing marks around the batched Huffman stages (ie_last_stage_ms): event i on the context's stream.
 int stage_mark(ie_ctx* c, int i) {
     if (!c->stage_timing) return IE_OK;  // (ie_set_stage_timing: off by default)
-    if (!c->stage_ev[i]) HIPCHK(c, hipEventCreate(&c->stage_ev[i]));
+    if (int r = c->stage_ev[i].create(c)) return r;
     HIPCHK(c, hipEventRecord(c->stage_ev[i], c->stream));
     if (i & 1) c->stage_rec[i >> 1] = true;
     return IE_OK;
@@ -139,7 +113,7 @@ int check_frames(ie_ctx* c, int w, int h, int nframes, size_t stride, size_t fra
 int stage_in(ie_ctx* c, const uint8_t* src, bool src_dev, size_t bytes, const uint8_t** dsrc) {
     *dsrc = src;
     if (src_dev || !bytes) return IE_OK;
-    int r = ensure(c, c->d_in, c->cap_in, bytes);
+    int r = c->d_in.reserve(c, bytes);
     if (r) return r;
     HIPCHK(c, hipMemcpyAsync(c->d_in, src, bytes, hipMemcpyHostToDevice, c->stream));
     *dsrc = c->d_in;
@@ -163,7 +137,7 @@ int ie_create(int device, ie_ctx** out) {
     // A BLOCKING stream: it orders with the legacy default (NULL) stream, so device buffers a caller
     // (e.g. PyTorch's default stream) filled just before a call are complete when the call's kernels
     // read them, and vice versa.  (Callers with their own streams use ie_set_stream.)
-    if (r == IE_OK) chk(hipStreamCreateWithFlags(&c->own, hipStreamDefault), "hipStreamCreate");
+    if (r == IE_OK) r = c->own.create(c, hipStreamDefault);
     c->stream = c->own;
     // Debug switch: order tiles by the atomic ticket from the first launch (exercises the
     // timeout-recovery path, which dispatch order otherwise never needs)
@@ -171,17 +145,17 @@ int ie_create(int device, ie_ctx** out) {
     // Debug switch: the next k synchronous error checks report a look-back timeout (exercises the
     // redo-in-ticket-mode paths and their output clearing)
     if (const char* ft = getenv("IE_FAKE_TIMEOUTS")) c->fake_timeouts = atoi(ft);
-    if (r == IE_OK) chk(hipMalloc(&c->d_tab, sizeof(ie::EncTables)), "hipMalloc(tables)");
-    if (r == IE_OK) chk(hipHostMalloc(&c->h_tab, sizeof(ie::EncTables)), "hipHostMalloc(tables)");
-    if (r == IE_OK) chk(hipMalloc(&c->d_ticket, sizeof(unsigned long long)), "hipMalloc(ticket)");
+    if (r == IE_OK) r = c->d_tab.reserve(c, 1);
+    if (r == IE_OK) r = c->h_tab.reserve(c, 1);
+    if (r == IE_OK) r = c->d_ticket.reserve(c, 1);
     if (r == IE_OK) chk(hipMemset(c->d_ticket, 0, sizeof(unsigned long long)), "hipMemset(ticket)");
-    if (r == IE_OK) chk(hipMalloc(&c->d_err, kErrWords * sizeof(unsigned)), "hipMalloc(err)");
+    if (r == IE_OK) r = c->d_err.reserve(c, kErrWords);
     if (r == IE_OK) chk(hipMemset(c->d_err, 0, kErrWords * sizeof(unsigned)), "hipMemset(err)");
-    if (r == IE_OK) chk(hipMalloc(&c->d_code, 2 * 256 * sizeof(uint32_t)), "hipMalloc(code)");
-    if (r == IE_OK) chk(hipHostMalloc(&c->h_code, 2 * 256 * sizeof(uint32_t)), "hipHostMalloc(code)");
-    if (r == IE_OK) chk(hipMalloc(&c->d_hist, 256 * sizeof(uint32_t)), "hipMalloc(hist)");
-    if (r == IE_OK) chk(hipMalloc(&c->d_misc, 8 * sizeof(uint64_t)), "hipMalloc(misc)");
-    if (r == IE_OK) chk(hipMalloc(&c->d_first, 256 * sizeof(unsigned long long)), "hipMalloc(first)");
+    if (r == IE_OK) r = c->d_code.reserve(c, 2 * 256);
+    if (r == IE_OK) r = c->h_code.reserve(c, 2 * 256);
+    if (r == IE_OK) r = c->d_hist.reserve(c, 256);
+    if (r == IE_OK) r = c->d_misc.reserve(c, 8);
+    if (r == IE_OK) r = c->d_first.reserve(c, 256);
     if (r != IE_OK) {
         std::fprintf(stderr, "ie_create: %s\n", c->err.c_str());
         ie_destroy(c);
@@ -196,26 +170,9 @@ int ie_destroy(ie_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->own) (void)hipStreamSynchronize(c->own);
     if (c->stream && c->stream != c->own) (void)hipStreamSynchronize(c->stream);
-    if (c->tab_stream) {
-        (void)hipStreamSynchronize(c->tab_stream);
-        (void)hipStreamDestroy(c->tab_stream);
-    }
-    for (void* d : std::initializer_list<void*>{
-             c->d_tab, c->d_state, c->d_ticket, c->d_frame_start, c->d_chain_end, c->d_err, c->d_wave_fix, c->d_in, c->d_out,
-             c->d_scratch, c->d_coef, c->d_code, c->d_hist, c->d_batch, c->d_chist, c->d_cslot[0], c->d_cslot[1], c->d_pack[0],
-             c->d_pack[1], c->d_first, c->d_dec, c->d_walk, c->d_count, c->d_rtab, c->d_rpos, c->d_misc, c->d_imgbits,
-             c->d_hlut, c->d_hout, c->d_hufb, c->d_hufb_res, c->d_pix, c->d_gop_rec, c->d_gop_coef, c->d_gop_bits, c->d_gop_tile, c->d_gop_pos,
-             c->d_gopg})
-        if (d) (void)hipFree(d);
-    for (void* h : std::initializer_list<void*>{c->h_tab, c->h_code, c->h_batch, c->h_hist[0], c->h_hist[1], c->h_pack[0],
-                                                c->h_pack[1], c->h_decres, c->h_imgres, c->h_hufb_res})
-        if (h) (void)hipHostFree(h);
-    for (hipEvent_t e : {c->ev_hist[0], c->ev_hist[1], c->ev_pack[0], c->ev_pack[1], c->ev_packed[0], c->ev_packed[1],
-                         c->stage_ev[0], c->stage_ev[1], c->stage_ev[2], c->stage_ev[3]})
-        if (e) (void)hipEventDestroy(e);
+    if (c->tab_stream) (void)hipStreamSynchronize(c->tab_stream);
     pipe_free(c->pipe);
-    if (c->own) (void)hipStreamDestroy(c->own);
-    delete c;
+    delete c;  // the buffers and events, then the streams
     return IE_OK;
 }
 
@@ -229,7 +186,7 @@ int ie_set_error(ie_ctx* c, const char* msg) {
 
 int ie_set_stream(ie_ctx* c, void* s) {
     if (!c) return IE_EINVAL;
-    c->stream = s ? static_cast<hipStream_t>(s) : c->own;
+    c->stream = s ? static_cast<hipStream_t>(s) : c->own.s;
     return IE_OK;
 }
 
@@ -282,7 +239,7 @@ int ie_cos_table(ie_ctx* c, double* out) {
     // read back from the DEVICE table: the values every kernel's FP64 path multiplies with
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, reinterpret_cast<const char*>(c->d_tab) + offsetof(ie::EncTables, c),
+    HIPCHK(c, hipMemcpy(out, reinterpret_cast<const char*>(c->d_tab.get()) + offsetof(ie::EncTables, c),
                         sizeof(double) * size_t(c->n) * size_t(c->n), hipMemcpyDeviceToHost));
     return IE_OK;
 }

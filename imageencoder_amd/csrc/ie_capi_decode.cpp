@@ -14,13 +14,12 @@ namespace {
 // The record stream on the device for the kernels' reads: whole aligned words up to the one holding
 // the last byte, then zeros (16 bytes of padding for the vector loads).  A 16-byte aligned device
 // stream is read in place unless `always`; anything else is copied (device copy or H2D) into buf.
-int stage_stream_in(ie_ctx* c, uint8_t*& buf, size_t& cap, const uint8_t* in, size_t len, bool always,
-                    const uint8_t** words) {
+int stage_stream_in(ie_ctx* c, Buf<uint8_t>& buf, const uint8_t* in, size_t len, bool always, const uint8_t** words) {
     const bool in_dev = is_device_ptr(in);
     *words = in;
     if (!always && in_dev && !(reinterpret_cast<uintptr_t>(in) & 15u)) return IE_OK;
     const size_t padded = (len + 3) / 4 * 4 + 16;
-    int r = ensure(c, buf, cap, padded);
+    int r = buf.reserve(c, padded);
     if (r) return r;
     HIPCHK(c, hipMemsetAsync(buf + (len / 4) * 4, 0, padded - (len / 4) * 4, c->stream));
     HIPCHK(c, hipMemcpyAsync(buf, in, len, in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
@@ -31,11 +30,11 @@ int stage_stream_in(ie_ctx* c, uint8_t*& buf, size_t& cap, const uint8_t* in, si
 // Where the kernels write pixels: a device destination itself, or buf (grown to span bytes) for a
 // host one -- which copy_frames_out then fills, pixel rows only (the bytes between rows and frames
 // belong to the caller).
-int pixel_dest(ie_ctx* c, uint8_t*& buf, size_t& cap, uint8_t* out, size_t span, bool* out_dev, uint8_t** dpix) {
+int pixel_dest(ie_ctx* c, Buf<uint8_t>& buf, uint8_t* out, size_t span, bool* out_dev, uint8_t** dpix) {
     *out_dev = is_device_ptr(out);
     *dpix = out;
     if (*out_dev) return IE_OK;
-    int r = ensure(c, buf, cap, span);
+    int r = buf.reserve(c, span);
     *dpix = buf;
     return r;
 }
@@ -45,14 +44,6 @@ int copy_frames_out(ie_ctx* c, uint8_t* out, const uint8_t* dpix, int f0, int f1
         HIPCHK(c, hipMemcpy2D(out + size_t(f) * frame_pitch, stride, dpix + size_t(f) * frame_pitch, stride, size_t(w),
                               size_t(h), hipMemcpyDeviceToHost));
     return IE_OK;
-}
-
-// Result words the device writes straight into pinned host memory (mapped, coherent): both views.
-int mapped_words(ie_ctx* c, size_t words, uint64_t** host, uint64_t** dev) {
-    void* hp = nullptr;
-    HIPCHK(c, hipHostMalloc(&hp, words * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent));
-    *host = static_cast<uint64_t*>(hp);
-    return device_view(c, *host, dev);
 }
 
 // The decode arguments every path shares; nframes, out, frame_pitch and add_base are the caller's.
@@ -138,10 +129,10 @@ int dec_scratch(ie_ctx* c, const RecPlan& pl, size_t batch, ie::RecParseArgs& a,
     const size_t cnt_at = even(batch * nch), wg_at = cnt_at + even(batch * nch), e_at = wg_at + even(batch * s.nwg);
     const size_t spec_at = e_at + even(batch * G), end = spec_at + (spec ? even(nch) : 0);
     int r;
-    if ((r = ensure(c, c->d_rtab, c->cap_rtab, batch * s.img_tab))) return r;
-    if ((r = ensure(c, c->d_rpos, c->cap_rpos, batch * nch * ie::kRecPosCap))) return r;
-    if ((r = ensure(c, c->d_walk, c->cap_walk, end / 2 + 1))) return r;
-    uint32_t* u32 = reinterpret_cast<uint32_t*>(c->d_walk);
+    if ((r = c->d_rtab.reserve(c, batch * s.img_tab))) return r;
+    if ((r = c->d_rpos.reserve(c, batch * nch * ie::kRecPosCap))) return r;
+    if ((r = c->d_walk.reserve(c, end / 2 + 1))) return r;
+    uint32_t* u32 = reinterpret_cast<uint32_t*>(c->d_walk.get());
     a.C = uint32_t(pl.C);
     a.nchunks = pl.nchunks;
     a.seg = s.seg;
@@ -180,7 +171,7 @@ struct DecProfile {
     double t0 = now(), t1 = 0, t2 = 0;
     const bool stats = getenv("IE_DEC_STATS") != nullptr;
     const char* stamps = getenv("IE_DEC_STAMPS");
-    uint64_t* d_ws = nullptr;
+    Buf<uint64_t> d_ws;
     size_t nws = 0;
     int begin(ie_ctx* c, ie::RecParseArgs& pa) {  // before the first launch
         if (stats) {
@@ -191,9 +182,9 @@ struct DecProfile {
         ie::rec_table_geometry(pa.C, c->n, &tm, &hb);
         nws = size_t(pa.nchunks + tm - 1) / size_t(tm) * 8;
         if (stamps) {
-            HIPCHK(c, hipMalloc(&d_ws, nws * 8));
+            if (int r = d_ws.reserve(c, nws)) return r;
             HIPCHK(c, hipMemsetAsync(d_ws, 0, nws * 8, c->stream));
-            pa.wstamp = reinterpret_cast<unsigned long long*>(d_ws);
+            pa.wstamp = reinterpret_cast<unsigned long long*>(d_ws.get());
         }
         t1 = now();
         return IE_OK;
@@ -216,7 +207,6 @@ struct DecProfile {
         if (d_ws) {
             std::vector<uint64_t> hws(nws);
             HIPCHK(c, hipMemcpy(hws.data(), d_ws, nws * 8, hipMemcpyDeviceToHost));
-            HIPCHK(c, hipFree(d_ws));
             if (FILE* f = fopen(stamps, "ab")) {
                 fwrite(hws.data(), 8, nws, f);
                 fclose(f);
@@ -252,7 +242,7 @@ int ie_decode_frames(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bi
     // (the kernels read the stream with 16-byte vector loads of whole aligned words up to the one
     // holding the last byte -- never past its page -- and clear the bits past the stream themselves)
     const uint8_t* words;
-    if ((r = stage_stream_in(c, c->d_dec, c->cap_dec, in, len, false, &words))) return r;
+    if ((r = stage_stream_in(c, c->d_dec, in, len, false, &words))) return r;
     const uint64_t nbits = uint64_t(len) * 8;
     const uint64_t nblocks = uint64_t(nframes) * (w / n) * (h / n);
     RecPlan pl{};
@@ -263,7 +253,7 @@ int ie_decode_frames(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bi
     int levels = pl.levels;
     bool out_dev;
     uint8_t* dpix;
-    if ((r = pixel_dest(c, c->d_pix, c->cap_pix, out, frames_span(nframes, frame_pitch, stride, w, h), &out_dev, &dpix)))
+    if ((r = pixel_dest(c, c->d_pix, out, frames_span(nframes, frame_pitch, stride, w, h), &out_dev, &dpix)))
         return r;
     ie::DecArgs da = dec_args(c, w, h, use_rle, stride);
     da.nframes = nframes;
@@ -273,9 +263,9 @@ int ie_decode_frames(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bi
     pa.nbits = nbits;
     pa.start_bit = start_bit;
     pa.rle = da.rle;
-    if (!c->h_decres && (r = mapped_words(c, 8, &c->h_decres, &c->d_decres))) return r;
-    pa.total = c->d_decres + 1;
-    pa.end_out = c->d_decres;
+    if ((r = c->h_decres.reserve(c, 8))) return r;
+    pa.total = c->h_decres.dev() + 1;
+    pa.end_out = c->h_decres.dev();
     // (the result words need no clearing: the last chunk's decode wave always writes the record total,
     // and the end bit is read only when that total covers the last block, whose decode writes it)
     if ((r = prof.begin(c, pa))) return r;
@@ -358,21 +348,11 @@ int ie_decode_images(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64
     batch = std::min<size_t>(batch, size_t(count));
     ie::RecParseArgs pa{};
     if ((r = dec_scratch(c, pl, batch, pa))) return r;
-    if ((r = ensure(c, c->d_imgbits, c->cap_imgbits, size_t(count)))) return r;
-    if (c->cap_imgres < size_t(count)) {
-        if (c->h_imgres) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, hipHostFree(c->h_imgres));
-            c->h_imgres = nullptr;
-            c->cap_imgres = 0;
-        }
-        const size_t cap = std::max<size_t>(size_t(count), 16);
-        if ((r = mapped_words(c, cap * 3, &c->h_imgres, &c->d_imgres))) return r;
-        c->cap_imgres = cap;
-    }
+    if ((r = c->d_imgbits.reserve(c, size_t(count)))) return r;
+    if ((r = c->h_imgres.reserve(c, 3 * std::max<size_t>(size_t(count), 16)))) return r;
     // the stream lengths: through pinned memory into a device array (every workgroup reads its
     // image's; a read of host memory per workgroup would cost more than the copy)
-    uint64_t* h_bits = c->h_imgres + 2 * c->cap_imgres;
+    uint64_t* h_bits = c->h_imgres + 2 * size_t(count);
     std::memcpy(h_bits, nbits, size_t(count) * sizeof(uint64_t));
     HIPCHK(c, hipMemcpyAsync(c->d_imgbits, h_bits, size_t(count) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     // streams: device slots that are 16-byte aligned, 16-byte pitched are read in place (16-byte
@@ -385,7 +365,7 @@ int ie_decode_images(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64
     if (!in_dev || (reinterpret_cast<uintptr_t>(in) & 15u) || (in_pitch & 15u)) {
         const size_t max_bytes = size_t((max_bits + 7) / 8);
         pitch = (max_bytes + 15) / 16 * 16 + 16;
-        if ((r = ensure(c, c->d_dec, c->cap_dec, pitch * size_t(count)))) return r;
+        if ((r = c->d_dec.reserve(c, pitch * size_t(count)))) return r;
         HIPCHK(c, hipMemsetAsync(c->d_dec, 0, pitch * size_t(count), c->stream));
         if (in_dev) {
             HIPCHK(c, hipMemcpy2DAsync(c->d_dec, pitch, in, in_pitch, std::min(max_bytes, in_pitch), size_t(count),
@@ -400,7 +380,7 @@ int ie_decode_images(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64
     }
     bool out_dev;
     uint8_t* dpix;
-    if ((r = pixel_dest(c, c->d_pix, c->cap_pix, out, frames_span(count, frame_pitch, stride, w, h), &out_dev, &dpix)))
+    if ((r = pixel_dest(c, c->d_pix, out, frames_span(count, frame_pitch, stride, w, h), &out_dev, &dpix)))
         return r;
     ie::DecArgs da = dec_args(c, w, h, use_rle, stride);
     da.nframes = 1;
@@ -413,8 +393,8 @@ int ie_decode_images(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64
         const int m = int(std::min(batch, size_t(count) - k0));
         pa.words = reinterpret_cast<const uint32_t*>(words + k0 * pitch);
         pa.img_nbits = c->d_imgbits + k0;
-        pa.end_out = c->d_imgres + 2 * k0;
-        pa.total = c->d_imgres + 2 * k0 + 1;
+        pa.end_out = c->h_imgres.dev() + 2 * k0;
+        pa.total = c->h_imgres.dev() + 2 * k0 + 1;
         da.out = dpix + k0 * frame_pitch;
         levels = ie::launch_rec_parse_decode_images(pa, da, n, m, c->stream);
         if (levels < 0) return fail(c, IE_EINVAL, "stream too long for one decode call");
@@ -462,10 +442,10 @@ int ie_decode_gop(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bit, 
     // the stream once on the device (16-byte aligned, zero padding for the vector reads), the
     // frames decoded into a device buffer (P-frames read their predecessor there)
     const uint8_t* words;
-    if ((r = stage_stream_in(c, c->d_in, c->cap_in, in, len, true, &words))) return r;
+    if ((r = stage_stream_in(c, c->d_in, in, len, true, &words))) return r;
     bool out_dev;
     uint8_t* dpix;
-    if ((r = pixel_dest(c, c->d_gop_rec, c->cap_gop_rec, out, frames_span(nframes, frame_pitch, stride, w, h), &out_dev,
+    if ((r = pixel_dest(c, c->d_gop_rec, out, frames_span(nframes, frame_pitch, stride, w, h), &out_dev,
                         &dpix)))
         return r;
     const int n = c->n, mv = mvec_bits(merange);
@@ -476,7 +456,7 @@ int ie_decode_gop(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bit, 
     // per-frame device words: pos[0..nframes] first bits (pos[f + 1] = frame f's end), tot[f]
     // records on frame f's true path; then the host copy of both
     const size_t nw = 2 * size_t(nframes) + 1;
-    if ((r = ensure(c, c->d_gop_pos, c->cap_gop_pos, nw))) return r;
+    if ((r = c->d_gop_pos.reserve(c, nw))) return r;
     uint64_t* pos = c->d_gop_pos;
     uint64_t* tot = pos + nframes + 1;
     ie::launch_gop_init(pos, tot, nframes, start_bit, c->stream);
@@ -499,7 +479,7 @@ int ie_decode_gop(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bit, 
     pa.rle = da.rle;
     pa.span = rec_bound;
     if (gop > 1 && nframes > 1 && !motioncomp)
-        if ((r = ensure(c, c->d_gop_coef, c->cap_gop_coef, (stride * size_t(h) + 1) / 2))) return r;
+        if ((r = c->d_gop_coef.reserve(c, (stride * size_t(h) + 1) / 2))) return r;
     for (int f = 0; f < nframes; f++) {
         uint8_t* fo = dpix + size_t(f) * frame_pitch;
         const bool iframe = (f % gop) == 0;
@@ -511,7 +491,7 @@ int ie_decode_gop(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bit, 
         // motion compensation the error is read (the stream must be consumed) but not applied:
         // decoded into scratch
         const bool apply = iframe || motioncomp;
-        da.out = apply ? fo : reinterpret_cast<uint8_t*>(c->d_gop_coef);
+        da.out = apply ? fo : reinterpret_cast<uint8_t*>(c->d_gop_coef.get());
         da.add_base = (apply && !iframe) ? 1 : 0;
         pa.dstart = pos + f;
         pa.start_add = iframe ? 0 : mvb;

@@ -130,7 +130,7 @@ int encode(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t fram
     } else {
         // stage from the word holding start_bit; its leading bytes carry the caller's header
         const size_t stage = span - size_t(w0) * 4;
-        if ((r = ensure(c, c->d_out, c->cap_out, stage))) return r;
+        if ((r = c->d_out.reserve(c, stage))) return r;
         for (int f = 0; f < (segmented ? nframes : 1); f++) {
             const size_t hb = size_t(f) * out_pitch + size_t(w0) * 4;
             uint8_t word[4] = {0, 0, 0, 0};
@@ -139,7 +139,7 @@ int encode(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t fram
             HIPCHK(c, hipMemcpyAsync(c->d_out + size_t(f) * out_pitch, word, 4, hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
-        dout = reinterpret_cast<uint32_t*>(c->d_out) - w0;
+        dout = reinterpret_cast<uint32_t*>(c->d_out.get()) - w0;
     }
 
     Launch L(dy, w, h, stride, frame_pitch, nframes, use_rle, mode, dout, start_bit);
@@ -253,8 +253,7 @@ int gop_wave_scratch(ie_ctx* c, int w, int h, int gop, int merange, size_t Gw, G
     W->Gw = Gw;
     const size_t sz_pos = align256((size_t(gop) + 1) * Gw * sizeof(uint64_t));
     const size_t sz_goff = align256((Gw + 1) * sizeof(uint64_t));
-    int r = ensure(c, c->d_gopg, c->cap_gopg,
-                   Gw * (W->sz_slot + W->sz_rec + W->sz_coef + W->sz_bits + W->sz_tile) + sz_pos + sz_goff);
+    int r = c->d_gopg.reserve(c, Gw * (W->sz_slot + W->sz_rec + W->sz_coef + W->sz_bits + W->sz_tile) + sz_pos + sz_goff);
     if (r) return r;
     uint8_t* p = c->d_gopg;
     auto carve = [&p](size_t bytes) {
@@ -354,12 +353,12 @@ int stage_gop_out(ie_ctx* c, uint8_t* out, bool out_dev, size_t need, uint64_t s
         *dout = reinterpret_cast<uint32_t*>(out);
         return IE_OK;
     }
-    int r = ensure(c, c->d_out, c->cap_out, need);
+    int r = c->d_out.reserve(c, need);
     if (r) return r;
     HIPCHK(c, hipMemsetAsync(c->d_out, 0, need, c->stream));
     const size_t hb = size_t((start_bit + 7) / 8);
     if (hb) HIPCHK(c, hipMemcpyAsync(c->d_out, out, hb, hipMemcpyHostToDevice, c->stream));
-    *dout = reinterpret_cast<uint32_t*>(c->d_out);
+    *dout = reinterpret_cast<uint32_t*>(c->d_out.get());
     return IE_OK;
 }
 
@@ -414,12 +413,12 @@ int ie_encode_gop(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size
     if ((r = stage_gop_out(c, out, out_dev, need, start_bit, &dout))) return r;
     const int n = c->n, bx = w / n, nb = bx * (h / n);
     if (has_p) {
-        if ((r = ensure(c, c->d_gop_rec, c->cap_gop_rec, 2 * size_t(w) * h))) return r;
-        if ((r = ensure(c, c->d_gop_coef, c->cap_gop_coef, size_t(nb) * 16))) return r;
-        if ((r = ensure(c, c->d_gop_bits, c->cap_gop_bits, size_t(nb)))) return r;
-        if ((r = ensure(c, c->d_gop_tile, c->cap_gop_tile, size_t(ie::pframe_tiles(nb)) + 1))) return r;
+        if ((r = c->d_gop_rec.reserve(c, 2 * size_t(w) * h))) return r;
+        if ((r = c->d_gop_coef.reserve(c, size_t(nb) * 16))) return r;
+        if ((r = c->d_gop_bits.reserve(c, size_t(nb)))) return r;
+        if ((r = c->d_gop_tile.reserve(c, size_t(ie::pframe_tiles(nb)) + 1))) return r;
     }
-    if ((r = ensure(c, c->d_gop_pos, c->cap_gop_pos, size_t(nframes) + 1))) return r;
+    if ((r = c->d_gop_pos.reserve(c, size_t(nframes) + 1))) return r;
     HIPCHK(c, hipMemcpy(c->d_gop_pos, &start_bit, sizeof(uint64_t), hipMemcpyHostToDevice));
 
     const uint8_t* ref = nullptr;
@@ -516,7 +515,7 @@ int ie_encode_gop_groups(ie_ctx* c, const uint8_t* y, int w, int h, size_t strid
     const int G = (nframes + gop - 1) / gop;
     GopWave W;
     if ((r = gop_wave_scratch(c, w, h, gop, merange, gop_wave_groups(c->n, w, h, gop, merange, size_t(G)), &W))) return r;
-    if ((r = ensure(c, c->d_gop_pos, c->cap_gop_pos, size_t(nframes) + 1))) return r;
+    if ((r = c->d_gop_pos.reserve(c, size_t(nframes) + 1))) return r;
     for (int g0 = 0; g0 < G; g0 += int(W.Gw)) {
         const int gw = std::min(int(W.Gw), G - g0);
         const int f0 = g0 * gop;  // (< nframes)
@@ -565,10 +564,10 @@ int ie_encode_images_counted(ie_ctx* c, const uint8_t* y, int w, int h, size_t s
     // memset before the launch only when they are not known to be zero
     const size_t K = size_t(nframes);
     int r;
-    if (c->cap_chist < K * 256 || !c->d_chist) {
-        if ((r = ensure(c, c->d_chist, c->cap_chist, K * 256))) return r;
-        HIPCHK(c, hipMemsetAsync(c->d_chist, 0, c->cap_chist * sizeof(uint32_t), c->stream));
-        c->chist_zero_rows = c->cap_chist / 256;
+    if (c->d_chist.cap() < K * 256 || !c->d_chist) {
+        if ((r = c->d_chist.reserve(c, K * 256))) return r;
+        HIPCHK(c, hipMemsetAsync(c->d_chist, 0, c->d_chist.cap() * sizeof(uint32_t), c->stream));
+        c->chist_zero_rows = c->d_chist.cap() / 256;
     }
     // rows [0, K) are counted into: skip their memset only when all of them are known zero (rows
     // of an earlier, larger batch that no fused pass cleared may hold stale counts)
@@ -588,12 +587,12 @@ int ie_quantize_frames(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride,
     int r = check_dims(c, w, h, nframes);
     if (r) return r;
     const size_t bound = ie_stream_bound(w, h, c->n, nframes, 0);
-    if ((r = ensure(c, c->d_scratch, c->cap_scratch, bound))) return r;
+    if ((r = c->d_scratch.reserve(c, bound))) return r;
     const size_t ncoef = size_t(nframes) * (w / c->n) * (h / c->n) * c->n * c->n;
     const bool dev = is_device_ptr(coef);
     int16_t* dc = coef;
     if (!dev) {
-        if ((r = ensure(c, c->d_coef, c->cap_coef, ncoef))) return r;
+        if ((r = c->d_coef.reserve(c, ncoef))) return r;
         dc = c->d_coef;
     }
     uint64_t end = 0;

@@ -33,12 +33,12 @@ int pack(ie_ctx* c, const uint8_t* bytes, size_t n, const uint32_t* code, const 
         if (reinterpret_cast<uintptr_t>(out) % 4) return fail(c, IE_EINVAL, "device output must be 4-byte aligned");
         dout = reinterpret_cast<uint32_t*>(out);
     } else {
-        if ((r = ensure(c, c->d_out, c->cap_out, need_bytes - size_t(w0) * 4))) return r;
+        if ((r = c->d_out.reserve(c, need_bytes - size_t(w0) * 4))) return r;
         uint8_t word[4] = {0, 0, 0, 0};
         for (int e = 0; e < 4 && size_t(w0) * 4 + e < out_cap; e++) word[e] = out[size_t(w0) * 4 + e];
         HIPCHK(c, hipMemcpyAsync(c->d_out, word, 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        dout = reinterpret_cast<uint32_t*>(c->d_out) - w0;
+        dout = reinterpret_cast<uint32_t*>(c->d_out.get()) - w0;
     }
     uint64_t end = start_bit;
     if (n) {
@@ -161,7 +161,7 @@ int huffman_decode_batch(ie_ctx* c, const uint8_t* in, size_t in_pitch, const ui
     size_t pitch = in_pitch;
     if (!in_dev || (reinterpret_cast<uintptr_t>(in) & 3u) || (in_pitch & 3u)) {
         pitch = (size_t(max_len) + 3) / 4 * 4 + 16;
-        if ((r = ensure(c, c->d_dec, c->cap_dec, pitch * K))) return r;
+        if ((r = c->d_dec.reserve(c, pitch * K))) return r;
         if (in_dev) {
             HIPCHK(c, hipMemcpy2DAsync(c->d_dec, pitch, in, in_pitch, size_t(max_len), K, hipMemcpyDeviceToDevice, c->stream));
         } else {
@@ -174,7 +174,7 @@ int huffman_decode_batch(ie_ctx* c, const uint8_t* in, size_t in_pitch, const ui
     }
     const uint16_t* dlut = lut;
     if (!is_device_ptr(lut) || reinterpret_cast<uintptr_t>(lut) % 2) {
-        if ((r = ensure(c, c->d_hlut, c->cap_hlut, K * 32768))) return r;
+        if ((r = c->d_hlut.reserve(c, K * 32768))) return r;
         HIPCHK(c, hipMemcpyAsync(c->d_hlut, lut, K * 32768 * sizeof(uint16_t),
                                  is_device_ptr(lut) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
         dlut = c->d_hlut;
@@ -182,13 +182,13 @@ int huffman_decode_batch(ie_ctx* c, const uint8_t* in, size_t in_pitch, const ui
     const bool out_dev = is_device_ptr(out);
     uint8_t* dout = out;
     if (!out_dev) {
-        if ((r = ensure(c, c->d_hout, c->cap_hout, K * out_pitch + 1))) return r;
+        if ((r = c->d_hout.reserve(c, K * out_pitch + 1))) return r;
         dout = c->d_hout;
     }
     // the lengths and first bits up, the flag pairs and totals cleared
-    if ((r = ensure(c, c->d_hufb_res, c->cap_hufb_res, 4 * K))) return r;
-    if ((r = ensure_pinned(c, c->h_hufb_res, c->cap_hhufb_res, 4 * K * sizeof(uint64_t) + K * head_bytes))) return r;
-    uint64_t* hres = reinterpret_cast<uint64_t*>(c->h_hufb_res);
+    if ((r = c->d_hufb_res.reserve(c, 4 * K))) return r;
+    if ((r = c->h_hufb_res.reserve(c, 4 * K * sizeof(uint64_t) + K * head_bytes))) return r;
+    uint64_t* hres = reinterpret_cast<uint64_t*>(c->h_hufb_res.get());
     uint8_t* hheads = c->h_hufb_res + 4 * K * sizeof(uint64_t);
     for (size_t k = 0; k < K; k++) {
         hres[k] = len[k] * 8;
@@ -204,12 +204,12 @@ int huffman_decode_batch(ie_ctx* c, const uint8_t* in, size_t in_pitch, const ui
         if (atoi(eb) > 0) batch = std::min<size_t>(batch, size_t(atoi(eb)));
     batch = std::min(batch, K);
     const HufScratch hs = huf_scratch(nch, batch);
-    if ((r = ensure(c, c->d_hufb, c->cap_hufb, hs.bytes))) return r;
+    if ((r = c->d_hufb.reserve(c, hs.bytes))) return r;
     ie::HufBatch b{};
     b.nchunks = int(nch);
     b.chunk_bits = chunk_bits;
     b.img_words = pitch / 4;
-    b.entry = reinterpret_cast<uint64_t*>(c->d_hufb);
+    b.entry = reinterpret_cast<uint64_t*>(c->d_hufb.get());
     b.base = reinterpret_cast<uint64_t*>(c->d_hufb + hs.base_at);
     b.tab = reinterpret_cast<uint16_t*>(c->d_hufb + hs.tab_at);
     b.count = reinterpret_cast<uint32_t*>(c->d_hufb + hs.count_at);
@@ -308,11 +308,11 @@ int ie_bitcopy(ie_ctx* c, const uint8_t* bytes, size_t n, uint8_t* out, size_t o
         return IE_OK;
     }
     // host output: stage from the word holding start_bit (its leading bytes keep the caller's bits)
-    if ((r = ensure(c, c->d_out, c->cap_out, need_bytes - size_t(w0) * 4))) return r;
+    if ((r = c->d_out.reserve(c, need_bytes - size_t(w0) * 4))) return r;
     uint8_t word[4] = {0, 0, 0, 0};
     for (int e = 0; e < 4 && size_t(w0) * 4 + e < out_cap; e++) word[e] = out[size_t(w0) * 4 + e];
     HIPCHK(c, hipMemcpyAsync(c->d_out, word, 4, hipMemcpyHostToDevice, c->stream));
-    ie::launch_bitshift(din, n, reinterpret_cast<uint32_t*>(c->d_out) - w0, start_bit, c->stream);
+    ie::launch_bitshift(din, n, reinterpret_cast<uint32_t*>(c->d_out.get()) - w0, start_bit, c->stream);
     HIPCHK(c, hipGetLastError());
     const size_t b0 = size_t(start_bit / 8), b1 = size_t((end + 7) / 8);
     HIPCHK(c, hipMemcpyAsync(out + b0, c->d_out + (b0 - size_t(w0) * 4), b1 - b0, hipMemcpyDeviceToHost, c->stream));
@@ -334,11 +334,11 @@ int ie_huffman_hist_batch(ie_ctx* c, const uint8_t* in, size_t in_pitch, const u
     const size_t hb = size_t(count) * 256 * sizeof(uint32_t), fb = size_t(count) * 256 * sizeof(uint64_t);
     const size_t nb = size_t(count) * sizeof(uint64_t), ub = size_t(count) * sizeof(unsigned);
     int r;
-    if ((r = ensure(c, c->d_batch, c->cap_batch, hb + fb + nb + ub))) return r;
-    if ((r = ensure_pinned(c, c->h_batch, c->cap_hbatch, nb))) return r;
+    if ((r = c->d_batch.reserve(c, hb + fb + nb + ub))) return r;
+    if ((r = c->h_batch.reserve(c, nb))) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the pinned staging may still feed a copy
     std::memcpy(c->h_batch, n, nb);
-    uint32_t* dh = reinterpret_cast<uint32_t*>(c->d_batch);
+    uint32_t* dh = reinterpret_cast<uint32_t*>(c->d_batch.get());
     auto* df = reinterpret_cast<unsigned long long*>(c->d_batch + hb);
     auto* dn = reinterpret_cast<uint64_t*>(c->d_batch + hb + fb);
     HIPCHK(c, hipMemcpyAsync(dn, c->h_batch, nb, hipMemcpyHostToDevice, c->stream));
@@ -360,8 +360,8 @@ int ie_huffman_hist_batch_ends(ie_ctx* c, const uint8_t* in, size_t in_pitch, co
     const size_t hb = size_t(count) * 256 * sizeof(uint32_t), fb = size_t(count) * 256 * sizeof(uint64_t);
     const size_t nb = size_t(count) * sizeof(uint64_t), ub = size_t(count) * sizeof(unsigned);
     int r;
-    if ((r = ensure(c, c->d_batch, c->cap_batch, hb + fb + nb + ub))) return r;
-    uint32_t* dh = reinterpret_cast<uint32_t*>(c->d_batch);
+    if ((r = c->d_batch.reserve(c, hb + fb + nb + ub))) return r;
+    uint32_t* dh = reinterpret_cast<uint32_t*>(c->d_batch.get());
     auto* df = reinterpret_cast<unsigned long long*>(c->d_batch + hb);
     auto* dn = reinterpret_cast<uint64_t*>(c->d_batch + hb + fb);
     auto* du = reinterpret_cast<unsigned*>(c->d_batch + hb + fb + nb);
@@ -383,17 +383,17 @@ int ie_huffman_hist_batch_ends_async(ie_ctx* c, const uint8_t* in, size_t in_pit
     const size_t hb = size_t(count) * 256 * sizeof(uint32_t), fb = size_t(count) * 256 * sizeof(uint64_t);
     const size_t nb = size_t(count) * sizeof(uint64_t), ub = size_t(count) * sizeof(unsigned);
     int r;
-    if ((r = ensure_pinned(c, c->h_hist[slot], c->cap_hhist[slot], hb + fb + ub))) return r;
-    if (!c->ev_hist[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_hist[slot], hipEventDisableTiming));
+    if ((r = c->h_hist[slot].reserve(c, hb + fb + ub))) return r;
+    if ((r = c->ev_hist[slot].create(c, hipEventDisableTiming))) return r;
     c->hist_fused[slot] = fused;
     c->hist_in[slot] = in;
     c->hist_pitch[slot] = in_pitch;
     if (fused) {
         // counts from the encoder (cleared as they are read), lengths from the end bits, results
         // straight into the pinned slot: ONE launch, no memset, no copy
-        if ((r = ensure(c, c->d_cslot[slot], c->cap_cslot[slot], fb + nb + ub))) return r;
+        if ((r = c->d_cslot[slot].reserve(c, fb + nb + ub))) return r;
         uint8_t* hp = nullptr;
-        if ((r = device_view(c, c->h_hist[slot], &hp))) return r;
+        if ((r = device_view(c, c->h_hist[slot].get(), &hp))) return r;
         uint8_t* ds = c->d_cslot[slot];
         if ((r = stage_mark(c, 0))) return r;
         ie::launch_first_counted(in, in_pitch, end_bits, uint64_t(in_pitch), count, c->d_chist,
@@ -408,8 +408,8 @@ int ie_huffman_hist_batch_ends_async(ie_ctx* c, const uint8_t* in, size_t in_pit
         c->hist_count[slot] = count;
         return IE_OK;
     }
-    if ((r = ensure(c, c->d_batch, c->cap_batch, hb + fb + nb + ub))) return r;
-    uint32_t* dh = reinterpret_cast<uint32_t*>(c->d_batch);
+    if ((r = c->d_batch.reserve(c, hb + fb + nb + ub))) return r;
+    uint32_t* dh = reinterpret_cast<uint32_t*>(c->d_batch.get());
     auto* df = reinterpret_cast<unsigned long long*>(c->d_batch + hb);
     auto* dn = reinterpret_cast<uint64_t*>(c->d_batch + hb + fb);
     auto* du = reinterpret_cast<unsigned*>(c->d_batch + hb + fb + nb);
@@ -450,14 +450,14 @@ int ie_huffman_hist_batch_wait(ie_ctx* c, int slot, uint32_t* hist, uint64_t* fi
                 maxn = std::max(maxn, s);
             }
             uint8_t* hp = nullptr;
-            if (int r = device_view(c, c->h_hist[slot], &hp)) return r;
+            if (int r = device_view(c, c->h_hist[slot].get(), &hp)) return r;
             // on the side stream, ordered after the batch's histogram only: work the caller queued on
             // c->stream since _async (e.g. the next batch's encode) is neither waited for nor
             // delayed, and only this launch and its read-back are synchronised
-            if (!c->tab_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->tab_stream, hipStreamNonBlocking));
+            if (int r = c->tab_stream.create(c, hipStreamNonBlocking)) return r;
             HIPCHK(c, hipStreamWaitEvent(c->tab_stream, c->ev_hist[slot], 0));
             ie::launch_first_full_batch(c->hist_in[slot], c->hist_pitch[slot], nn, maxn, K, reinterpret_cast<const uint32_t*>(hp),
-                                        reinterpret_cast<unsigned long long*>(c->d_cslot[slot]),
+                                        reinterpret_cast<unsigned long long*>(c->d_cslot[slot].get()),
                                         reinterpret_cast<const unsigned*>(c->d_cslot[slot] + fb + nb), c->tab_stream);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipMemcpyAsync(first_pos, c->d_cslot[slot], fb, hipMemcpyDeviceToHost, c->tab_stream));
@@ -514,12 +514,12 @@ int ie_huffman_pack_batch(ie_ctx* c, const uint8_t* in, size_t in_pitch, const u
     const int ps = c->pack_slot;
     c->pack_slot ^= 1;
     if (c->pack_recorded[ps]) HIPCHK(c, hipEventSynchronize(c->ev_pack[ps]));
-    if ((r = ensure_pinned(c, c->h_pack[ps], c->cap_hpack[ps], total))) return r;
-    if (c->cap_dpack[ps] < total && c->d_pack[ps]) HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((r = ensure(c, c->d_pack[ps], c->cap_dpack[ps], total))) return r;
-    if (!c->ev_pack[ps]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_pack[ps], hipEventDisableTiming));
-    if (!c->ev_packed[ps]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_packed[ps], hipEventDisableTiming));
-    if (!c->tab_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->tab_stream, hipStreamNonBlocking));
+    if ((r = c->h_pack[ps].reserve(c, total))) return r;
+    if (c->d_pack[ps].cap() < total && c->d_pack[ps]) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((r = c->d_pack[ps].reserve(c, total))) return r;
+    if ((r = c->ev_pack[ps].create(c, hipEventDisableTiming))) return r;
+    if ((r = c->ev_packed[ps].create(c, hipEventDisableTiming))) return r;
+    if ((r = c->tab_stream.create(c, hipStreamNonBlocking))) return r;
     uint8_t* h = c->h_pack[ps];
     std::memcpy(h + o_ts, ts.data(), 8 * (K + 1));
     std::memcpy(h + o_n, n, 8 * K);
@@ -680,7 +680,7 @@ int ie_huffman_decode(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_b
     const uint8_t* src = in;
     if (!is_device_ptr(in) || reinterpret_cast<uintptr_t>(in) % 4) {
         const size_t padded = (len + 3) / 4 * 4 + 16;
-        if ((r = ensure(c, c->d_dec, c->cap_dec, padded))) return r;
+        if ((r = c->d_dec.reserve(c, padded))) return r;
         if (len)
             HIPCHK(c, hipMemcpyAsync(c->d_dec, in, len, is_device_ptr(in) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                                      c->stream));
@@ -688,7 +688,7 @@ int ie_huffman_decode(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_b
     }
     const uint16_t* dlut = lut;
     if (!is_device_ptr(lut) || reinterpret_cast<uintptr_t>(lut) % 2) {
-        if ((r = ensure(c, c->d_hlut, c->cap_hlut, size_t(32768)))) return r;
+        if ((r = c->d_hlut.reserve(c, size_t(32768)))) return r;
         HIPCHK(c, hipMemcpyAsync(c->d_hlut, lut, 32768 * sizeof(uint16_t),
                                  is_device_ptr(lut) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
         dlut = c->d_hlut;
@@ -698,12 +698,12 @@ int ie_huffman_decode(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_b
     const size_t nchunks = size_t((nbits - start_bit + chunk_bits - 1) / chunk_bits);
     if (!nchunks) return IE_OK;
     // d_walk: [cap] entries, [cap] symbol bases, then 128 words of top-level entries (256 x u32)
-    if ((r = ensure(c, c->d_walk, c->cap_walk, 2 * nchunks + 130))) return r;
+    if ((r = c->d_walk.reserve(c, 2 * nchunks + 130))) return r;
     // per-chunk symbol counts, then the walk workgroups' totals (ie::kTPB chunks each)
-    if ((r = ensure(c, c->d_count, c->cap_count, nchunks + (nchunks + ie::kTPB - 1) / ie::kTPB + 1))) return r;
-    if ((r = ensure(c, c->d_rtab, c->cap_rtab, ie::huffman_table_rows(nbits, start_bit, chunk_bits) + 2))) return r;
+    if ((r = c->d_count.reserve(c, nchunks + (nchunks + ie::kTPB - 1) / ie::kTPB + 1))) return r;
+    if ((r = c->d_rtab.reserve(c, ie::huffman_table_rows(nbits, start_bit, chunk_bits) + 2))) return r;
     uint64_t* wk = c->d_walk;
-    const size_t cap = (c->cap_walk - 130) / 2;
+    const size_t cap = (c->d_walk.cap() - 130) / 2;
     unsigned* flags = reinterpret_cast<unsigned*>(c->d_misc + 1);
     uint32_t* E = reinterpret_cast<uint32_t*>(wk + 2 * cap);
     unsigned* ticket = reinterpret_cast<unsigned*>(c->d_misc + 5);
@@ -734,7 +734,7 @@ int ie_huffman_decode(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_b
     *nout = size_t(total);
     if (total > out_cap) return fail(c, IE_ECAP, "output capacity below the decoded symbol count");
     // (a host destination from here on: the symbols are emitted into d_hout)
-    if ((r = ensure(c, c->d_hout, c->cap_hout, size_t(total) + 1))) return r;
+    if ((r = c->d_hout.reserve(c, size_t(total) + 1))) return r;
     uint8_t* dout = c->d_hout;
     ie::huffman_decode_device(W, nbits, start_bit, dlut, chunk_bits, wk, c->d_rtab, E, ticket, c->d_count,
                               wk + cap, flags, c->d_misc + 2, dout, true, c->stream);

@@ -10,27 +10,28 @@
 #include "ie_ctx.hpp"
 
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <thread>
 
 using namespace iec;
 
+// The slot buffers are resized with Wait::None: a slot is only resized when nothing of this run
+// uses it yet, and later chunks may still be encoding on the context's stream.
 struct ie_pipe {
-    hipStream_t h2d = nullptr, d2h = nullptr;
-    hipEvent_t ev_h2d[2] = {}, ev_enc[2] = {}, ev_d2h[2] = {};
+    Stream h2d, d2h;  // (first: destroyed after the events and buffers below)
+    Event ev_h2d[2], ev_enc[2], ev_d2h[2];
     bool rec_enc[2] = {}, rec_d2h[2] = {}, rec_h2d[2] = {};
-    uint8_t* d_in[2] = {};
-    size_t cap_din[2] = {};
-    uint8_t* d_out[2] = {};
-    size_t cap_dout[2] = {};
-    uint8_t* h_in[2] = {};
-    size_t cap_hin[2] = {};
-    uint8_t* h_out[2] = {};
-    size_t cap_hout[2] = {};
-    uint64_t* h_ends = nullptr;    // pinned [2][kMaxChunk + 1]: images: each image's chain end;
-                                   // video chunks: the frame starts, then [kMaxChunk] the chain end
-    uint32_t* h_hdr = nullptr;     // pinned [2][kMaxChunk] header words (the word holding start_bit)
-    uint64_t* d_ends = nullptr;    // device [2]: chained launches read the previous end here
+    Buf<uint8_t> d_in[2], d_out[2];
+    Buf<uint8_t, Mem::Pinned> h_in[2], h_out[2];
+    Buf<uint64_t, Mem::Pinned> h_ends;  // [2][kMaxChunk + 1]: images: each image's chain end;
+                                        // video chunks: the frame starts, then [kMaxChunk] the chain end
+    Buf<uint32_t, Mem::Pinned> h_hdr;   // [2][kMaxChunk] header words (the word holding start_bit)
+    Buf<uint64_t> d_ends;               // [2]: chained launches read the previous end here
+    ~ie_pipe() {
+        if (h2d) (void)hipStreamSynchronize(h2d);
+        if (d2h) (void)hipStreamSynchronize(d2h);
+    }
 };
 
 // ---- streamed video (ie_vstream_*) ----------------------------------------------------------
@@ -50,22 +51,22 @@ struct ie_vstream {
     int w = 0, h = 0, rle = 1, mode = IE_MODE_FAST;
     int gop = 1, merange = 0;
     int fill = 0;                    // gop > 1: frames in the current input slot, not launched yet
-    uint64_t* d_pos = nullptr;       // gop > 1: device [max_frames + 1] first bit of every launched frame; a
+    Buf<uint64_t> d_pos;             // gop > 1: [max_frames + 1] first bit of every launched frame; a
                                      // chunk's end bit lies where the next chunk's first frame goes
-    uint64_t* h_pos = nullptr;       // gop > 1: pinned [2][K + 1] read-back of a chunk's part of d_pos
+    Buf<uint64_t, Mem::Pinned> h_pos;  // gop > 1: [2][K + 1] read-back of a chunk's part of d_pos
     size_t stride = 0, frame_pitch = 0;
     uint64_t start_bit = 0;
     int max_frames = 0, frames = 0;  // capacity, frames launched
     int K = 1;                       // frames per chunk
-    uint8_t* d_stream = nullptr;     // the whole stream from byte 0 (the caller's head included)
-    size_t cap = 0;
+    Buf<uint8_t> d_stream;           // the whole stream from byte 0 (the caller's head included)
     int chunks = 0;                  // chunks launched
     int harvested = 0;               // chunks whose frame starts / end are known on the host
     uint64_t done_bits = 0;          // chain end of the last harvested chunk
     uint64_t pulled = 0;             // bytes [0, pulled) handed out by ie_vstream_pull
     int chunk_f0[2] = {}, chunk_nf[2] = {};
     std::vector<uint64_t> fs;        // absolute start bit of every harvested frame
-    ie_pipe* P = nullptr;            // its own streams, events and slots
+    ie_pipe P;                       // its own streams, events and slots (last: its streams are
+                                     // synchronised before anything above is freed)
 };
 
 namespace {
@@ -93,26 +94,23 @@ void par_copy(uint8_t* dst, const uint8_t* src, size_t n) {
 using Pipe = ie_pipe;
 constexpr int kMaxChunk = 64;
 
-int pipe_new(ie_ctx* c, Pipe*& P) {
-    P = new Pipe();
-    HIPCHK(c, hipStreamCreateWithFlags(&P->h2d, hipStreamNonBlocking));
-    HIPCHK(c, hipStreamCreateWithFlags(&P->d2h, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++) {
-        HIPCHK(c, hipEventCreateWithFlags(&P->ev_h2d[i], hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&P->ev_enc[i], hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&P->ev_d2h[i], hipEventDisableTiming));
-    }
-    HIPCHK(c, hipHostMalloc(&P->h_ends, 2 * (kMaxChunk + 1) * sizeof(uint64_t)));
-    HIPCHK(c, hipHostMalloc(&P->h_hdr, 2 * kMaxChunk * sizeof(uint32_t)));
-    HIPCHK(c, hipMalloc(&P->d_ends, 2 * sizeof(uint64_t)));
-    return IE_OK;
+int pipe_init(ie_ctx* c, Pipe* P) {
+    int r;
+    if ((r = P->h2d.create(c, hipStreamNonBlocking)) || (r = P->d2h.create(c, hipStreamNonBlocking))) return r;
+    for (int i = 0; i < 2; i++)
+        if ((r = P->ev_h2d[i].create(c, hipEventDisableTiming)) || (r = P->ev_enc[i].create(c, hipEventDisableTiming)) ||
+            (r = P->ev_d2h[i].create(c, hipEventDisableTiming)))
+            return r;
+    if ((r = P->h_ends.reserve(c, 2 * (kMaxChunk + 1))) || (r = P->h_hdr.reserve(c, 2 * kMaxChunk))) return r;
+    return P->d_ends.reserve(c, 2);
 }
 
 // The context's pipeline for streamed image batches; a new run starts with nothing pending (the
 // previous one ended with a full synchronisation).
 int pipe_get(ie_ctx* c, Pipe*& P) {
     if (!c->pipe) {
-        int r = pipe_new(c, c->pipe);
+        c->pipe = new Pipe();
+        int r = pipe_init(c, c->pipe);
         if (r) {
             pipe_free(c->pipe);
             c->pipe = nullptr;
@@ -121,24 +119,6 @@ int pipe_get(ie_ctx* c, Pipe*& P) {
     }
     P = c->pipe;
     for (int i = 0; i < 2; i++) P->rec_enc[i] = P->rec_d2h[i] = P->rec_h2d[i] = false;
-    return IE_OK;
-}
-
-// device / pinned slot buffers (a slot is only resized when nothing of this run uses it yet)
-int slot_dev(ie_ctx* c, uint8_t*& p, size_t& cap, size_t need) {
-    if (cap >= need && p) return IE_OK;
-    if (p) HIPCHK(c, hipFree(p));
-    p = nullptr;
-    HIPCHK(c, hipMalloc(&p, need));
-    cap = need;
-    return IE_OK;
-}
-int slot_pinned(ie_ctx* c, uint8_t*& p, size_t& cap, size_t need) {
-    if (cap >= need && p) return IE_OK;
-    if (p) HIPCHK(c, hipHostFree(p));
-    p = nullptr;
-    HIPCHK(c, hipHostMalloc(&p, need));
-    cap = need;
     return IE_OK;
 }
 
@@ -176,7 +156,7 @@ int pipe_upload(ie_ctx* c, Pipe* P, int s, const uint8_t* y, size_t frame_pitch,
 // The host side of chunk j (the oldest unharvested one): its frame starts and chain end.
 int vs_harvest(ie_vstream* v) {
     ie_ctx* c = v->c;
-    Pipe* P = v->P;
+    Pipe* P = &v->P;
     const int j = v->harvested, s = j & 1;
     HIPCHK(c, hipEventSynchronize(P->ev_enc[s]));
     const uint64_t* hs = v->gop > 1 ? v->h_pos + size_t(s) * size_t(v->K + 1) : P->h_ends + s * (kMaxChunk + 1);
@@ -189,7 +169,7 @@ int vs_harvest(ie_vstream* v) {
 // One chunk: upload, then a launch continuing the chain on the device.
 int vs_chunk(ie_vstream* v, const uint8_t* frames, int nf, bool pinned_in) {
     ie_ctx* c = v->c;
-    Pipe* P = v->P;
+    Pipe* P = &v->P;
     const int k = v->chunks, s = k & 1;
     while (k - v->harvested >= 2) {  // slot s's read-back area still holds chunk k-2's ends
         int r = vs_harvest(v);
@@ -200,7 +180,7 @@ int vs_chunk(ie_vstream* v, const uint8_t* frames, int nf, bool pinned_in) {
     if ((r = pipe_upload(c, P, s, frames, v->frame_pitch, ib, 0, pinned_in))) return r;
     HIPCHK(c, hipStreamWaitEvent(c->stream, P->ev_h2d[s], 0));
     Launch L(P->d_in[s], v->w, v->h, v->stride, v->frame_pitch, nf, v->rle, v->mode,
-             reinterpret_cast<uint32_t*>(v->d_stream), v->start_bit);
+             reinterpret_cast<uint32_t*>(v->d_stream.get()), v->start_bit);
     L.start_dev = k ? P->d_ends + ((k - 1) & 1) : nullptr;
     L.chain_end = P->d_ends + s;
     if ((r = launch_chain(c, L))) return r;
@@ -220,7 +200,7 @@ int vs_chunk(ie_vstream* v, const uint8_t* frames, int nf, bool pinned_in) {
 // gop > 1: launch the v->fill frames gathered in the current input slot as one wave of groups.
 int vs_gop_launch(ie_vstream* v) {
     ie_ctx* c = v->c;
-    Pipe* P = v->P;
+    Pipe* P = &v->P;
     const int k = v->chunks, s = k & 1, nfw = v->fill, gw = (nfw + v->gop - 1) / v->gop;
     int r;
     while (k - v->harvested >= 2)  // slot s's read-back area still holds chunk k-2's positions
@@ -231,7 +211,7 @@ int vs_gop_launch(ie_vstream* v) {
     if ((r = gop_wave_scratch(c, v->w, v->h, v->gop, v->merange, size_t(v->K / v->gop), &W))) return r;
     uint64_t* fpos = v->d_pos + v->frames;  // fpos[0] holds the previous chunk's end bit
     if ((r = launch_gop_wave(c, W, P->d_in[s], v->w, v->h, v->stride, v->frame_pitch, gw, nfw, v->merange, v->rle, v->mode,
-                             reinterpret_cast<uint32_t*>(v->d_stream), v->start_bit, k ? fpos : nullptr, fpos)))
+                             reinterpret_cast<uint32_t*>(v->d_stream.get()), v->start_bit, k ? fpos : nullptr, fpos)))
         return r;
     HIPCHK(c, hipMemcpyAsync(v->h_pos + size_t(s) * size_t(v->K + 1), fpos, size_t(nfw + 1) * sizeof(uint64_t),
                              hipMemcpyDeviceToHost, c->stream));
@@ -250,7 +230,7 @@ int vs_gop_launch(ie_vstream* v) {
 int vs_gop_push(ie_vstream* v, const uint8_t* frames, int nframes, bool pinned_in) {
     for (int f = 0; f < nframes;) {
         const int s = v->chunks & 1, nf = std::min(v->K - v->fill, nframes - f);
-        int r = pipe_upload(v->c, v->P, s, frames, v->frame_pitch, frames_span(nf, v->frame_pitch, v->stride, v->w, v->h),
+        int r = pipe_upload(v->c, &v->P, s, frames, v->frame_pitch, frames_span(nf, v->frame_pitch, v->stride, v->w, v->h),
                             f, pinned_in, size_t(v->fill) * v->frame_pitch);
         if (r) return r;
         v->fill += nf;
@@ -265,7 +245,7 @@ int vs_gop_push(ie_vstream* v, const uint8_t* frames, int nframes, bool pinned_i
 // host copies piece i out while piece i+1 is in flight).
 int vs_copy_out(ie_vstream* v, uint8_t* dst, uint64_t b1) {
     ie_ctx* c = v->c;
-    Pipe* P = v->P;
+    Pipe* P = &v->P;
     if (b1 <= v->pulled) return IE_OK;
     const size_t n = size_t(b1 - v->pulled);
     const uint8_t* src = v->d_stream + v->pulled;
@@ -278,7 +258,7 @@ int vs_copy_out(ie_vstream* v, uint8_t* dst, uint64_t b1) {
         constexpr size_t kPiece = size_t(16) << 20;
         int r;
         for (int s = 0; s < 2; s++)
-            if ((r = slot_pinned(c, P->h_out[s], P->cap_hout[s], std::min(n, kPiece)))) return r;
+            if ((r = P->h_out[s].reserve(c, std::min(n, kPiece), Wait::None))) return r;
         const size_t pieces = (n + kPiece - 1) / kPiece;
         for (size_t i = 0; i <= pieces; i++) {
             if (i < pieces) {  // slot i&1 was emptied at step i-1
@@ -297,14 +277,6 @@ int vs_copy_out(ie_vstream* v, uint8_t* dst, uint64_t b1) {
     return IE_OK;
 }
 
-void vs_free(ie_vstream* v) {
-    pipe_free(v->P);
-    (void)hipFree(v->d_stream);
-    (void)hipFree(v->d_pos);
-    if (v->h_pos) (void)hipHostFree(v->h_pos);
-    delete v;
-}
-
 // ie_vstream_open (gop = 1) and ie_vstream_open_gop (gop > 1)
 int vs_open(ie_ctx* c, int w, int h, size_t stride, size_t frame_pitch, int gop, int merange, int use_rle, int mode,
             const uint8_t* head, uint64_t start_bit, int max_frames, ie_vstream** out) {
@@ -318,12 +290,9 @@ int vs_open(ie_ctx* c, int w, int h, size_t stride, size_t frame_pitch, int gop,
         return r;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    ie_vstream* v = new ie_vstream();
-    if ((r = pipe_new(c, v->P))) {
-        vs_free(v);
-        return r;
-    }
-    Pipe* P = v->P;
+    std::unique_ptr<ie_vstream> v(new ie_vstream());
+    Pipe* P = &v->P;
+    if ((r = pipe_init(c, P))) return r;
     v->c = c;
     v->w = w;
     v->h = h;
@@ -346,20 +315,13 @@ int vs_open(ie_ctx* c, int w, int h, size_t stride, size_t frame_pitch, int gop,
     }
     v->fs.assign(size_t(max_frames), 0);
     v->done_bits = start_bit;
-    v->cap = gop > 1 ? gop_cap : ie_stream_bound(w, h, c->n, max_frames, start_bit);
+    const size_t cap = gop > 1 ? gop_cap : ie_stream_bound(w, h, c->n, max_frames, start_bit);
     const size_t in_bytes = frames_span(v->K, frame_pitch, stride, w, h);
-    auto bad = [&](int code) {
-        vs_free(v);
-        return code;
-    };
-    if (hipMalloc(&v->d_stream, v->cap) != hipSuccess) return bad(fail(c, IE_EHIP, "hipMalloc(video stream)"));
-    if (gop > 1 && (hipMalloc(&v->d_pos, (size_t(max_frames) + 1) * sizeof(uint64_t)) != hipSuccess ||
-                    hipHostMalloc(&v->h_pos, 2 * size_t(v->K + 1) * sizeof(uint64_t)) != hipSuccess))
-        return bad(fail(c, IE_EHIP, "hipMalloc(video stream positions)"));
-    for (int s = 0; s < 2; s++) {
-        if ((r = slot_dev(c, P->d_in[s], P->cap_din[s], in_bytes))) return bad(r);
-        if ((r = slot_pinned(c, P->h_in[s], P->cap_hin[s], in_bytes))) return bad(r);
-    }
+    if ((r = v->d_stream.reserve(c, cap))) return r;
+    if (gop > 1 && ((r = v->d_pos.reserve(c, size_t(max_frames) + 1)) || (r = v->h_pos.reserve(c, 2 * size_t(v->K + 1)))))
+        return r;
+    for (int s = 0; s < 2; s++)
+        if ((r = P->d_in[s].reserve(c, in_bytes, Wait::None)) || (r = P->h_in[s].reserve(c, in_bytes, Wait::None))) return r;
     // the caller's head: bytes [0, ceil(start_bit/8)), bits from start_bit on cleared; the word
     // holding start_bit is completed by the first chunk's first tile.  gop > 1: the splice ORs every
     // group's first and last word into the stream, so all of it starts as zeros.
@@ -367,11 +329,11 @@ int vs_open(ie_ctx* c, int w, int h, size_t stride, size_t frame_pitch, int gop,
     std::vector<uint8_t> hd(hb + 8, 0);
     if (hb) std::memcpy(hd.data(), head, hb);
     if (start_bit % 8) hd[hb - 1] &= uint8_t(0xFF00u >> (start_bit % 8));
-    if (hipMemsetAsync(v->d_stream, 0, gop > 1 ? v->cap : std::min(v->cap, hb + 8), c->stream) != hipSuccess ||
+    if (hipMemsetAsync(v->d_stream, 0, gop > 1 ? cap : std::min(cap, hb + 8), c->stream) != hipSuccess ||
         (hb && hipMemcpyAsync(v->d_stream, hd.data(), hb, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
         hipStreamSynchronize(c->stream) != hipSuccess)
-        return bad(fail(c, IE_EHIP, "video stream head upload"));
-    *out = v;
+        return fail(c, IE_EHIP, "video stream head upload");
+    *out = v.release();
     return IE_OK;
 }
 
@@ -399,7 +361,7 @@ int ie_vstream_push(ie_vstream* v, const uint8_t* frames, int nframes) {
     if (ie_is_device_ptr(frames)) return fail(c, IE_EINVAL, "ie_vstream_push takes host frames");
     HIPCHK(c, hipSetDevice(c->device));
     // the previous push's pinned frames may still be in flight: they are released now
-    HIPCHK(c, hipStreamSynchronize(v->P->h2d));
+    HIPCHK(c, hipStreamSynchronize(v->P.h2d));
     const bool pinned = is_pinned_ptr(frames);
     if (v->gop > 1) return vs_gop_push(v, frames, nframes, pinned);
     for (int f = 0; f < nframes; f += v->K) {
@@ -459,7 +421,7 @@ int ie_vstream_close(ie_vstream* v) {
     if (!v) return IE_OK;
     ie_ctx* c = v->c;
     (void)hipStreamSynchronize(c->stream);
-    vs_free(v);
+    delete v;
     return IE_OK;
 }
 
@@ -467,26 +429,7 @@ int ie_vstream_close(ie_vstream* v) {
 
 namespace iec {
 
-void pipe_free(Pipe* p) {
-    if (!p) return;
-    if (p->h2d) (void)hipStreamSynchronize(p->h2d);
-    if (p->d2h) (void)hipStreamSynchronize(p->d2h);
-    for (int i = 0; i < 2; i++) {
-        (void)hipFree(p->d_in[i]);
-        (void)hipFree(p->d_out[i]);
-        if (p->h_in[i]) (void)hipHostFree(p->h_in[i]);
-        if (p->h_out[i]) (void)hipHostFree(p->h_out[i]);
-        if (p->ev_h2d[i]) (void)hipEventDestroy(p->ev_h2d[i]);
-        if (p->ev_enc[i]) (void)hipEventDestroy(p->ev_enc[i]);
-        if (p->ev_d2h[i]) (void)hipEventDestroy(p->ev_d2h[i]);
-    }
-    if (p->h_ends) (void)hipHostFree(p->h_ends);
-    if (p->h_hdr) (void)hipHostFree(p->h_hdr);
-    (void)hipFree(p->d_ends);
-    if (p->h2d) (void)hipStreamDestroy(p->h2d);
-    if (p->d2h) (void)hipStreamDestroy(p->d2h);
-    delete p;
-}
+void pipe_free(Pipe* p) { delete p; }  // (~ie_pipe waits for its two streams first)
 
 int streamed_images(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,
                     int use_rle, int mode, uint8_t* out, size_t out_pitch, uint64_t start_bit, uint64_t* end_bits) {
@@ -504,10 +447,8 @@ int streamed_images(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, si
     const uint64_t w0 = start_bit / 32;
     const size_t b0 = size_t(start_bit / 8);
     const size_t stage = out_pitch * size_t(K - 1) + (out_pitch - size_t(w0) * 4);  // slot: from word w0 of image 0
-    for (int s = 0; s < 2; s++) {
-        if ((r = slot_dev(c, P->d_in[s], P->cap_din[s], in_bytes))) return r;
-        if ((r = slot_dev(c, P->d_out[s], P->cap_dout[s], stage))) return r;
-    }
+    for (int s = 0; s < 2; s++)
+        if ((r = P->d_in[s].reserve(c, in_bytes, Wait::None)) || (r = P->d_out[s].reserve(c, stage, Wait::None))) return r;
     std::vector<uint64_t> ends(size_t(nframes), 0);
     // hand-offs between the three threads: counters of chunks whose H2D / encode / D2H are
     // issued, waited on by spinning (a condition variable's wake-up costs tens of microseconds
@@ -572,8 +513,8 @@ int streamed_images(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, si
         // page-locked memory (h_hdr[s] is free: chunk k-2's encode has completed)
         uint32_t* hw = P->h_hdr + s * kMaxChunk;
         for (int i = 0; i < nf; i++) std::memcpy(&hw[i], out + size_t(f0 + i) * out_pitch + size_t(w0) * 4, 4);
-        ie::launch_word_scatter(hw, reinterpret_cast<uint32_t*>(P->d_out[s]), out_pitch / 4, nf, c->stream);
-        Launch L(P->d_in[s], w, h, stride, frame_pitch, nf, use_rle, mode, reinterpret_cast<uint32_t*>(P->d_out[s]) - w0,
+        ie::launch_word_scatter(hw, reinterpret_cast<uint32_t*>(P->d_out[s].get()), out_pitch / 4, nf, c->stream);
+        Launch L(P->d_in[s], w, h, stride, frame_pitch, nf, use_rle, mode, reinterpret_cast<uint32_t*>(P->d_out[s].get()) - w0,
                  start_bit);
         L.out_pitch = out_pitch;
         L.segmented = 1;

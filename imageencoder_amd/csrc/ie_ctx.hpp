@@ -1,6 +1,12 @@
 // imageencoder_amd/csrc/ie_ctx.hpp -- internal to the C ABI implementation (ie_capi*.cpp,
-// ie_tables.cpp): the context, its allocators, and the checks and staging steps the entry points
-// share.  Functions that cross a file boundary are declared here, in namespace iec, and nowhere else.
+// ie_tables.cpp): the context, the owners of its memory and handles (Buf, Event, Stream), and the
+// checks and staging steps the entry points share.  Functions that cross a file boundary are
+// declared here, in namespace iec, and nowhere else.
+//
+// Every device or pinned allocation of the context, of a streamed pipeline and of a video stream
+// is a Buf member: it holds the pointer and the capacity, grows through reserve() and frees itself
+// when its owner is deleted.  A new buffer is one member and its reserve() calls; no teardown code
+// names it.  Events and side streams are Event / Stream members in the same way.
 #pragma once
 #include "ie_hip.h"
 
@@ -28,38 +34,106 @@
 #endif
 
 struct ie_pipe;  // streamed host path (ie_capi_stream.cpp)
+struct ie_ctx;
 
 namespace iec {
 constexpr int kErrWords = 66;  // d_err: [0] look-back timeouts; sum of [2..65] = FP64 re-evaluations
-}
+
+// Device: hipMalloc.  Pinned: hipHostMalloc.  Mapped: pinned memory the device writes directly
+// (hipHostMallocMapped | hipHostMallocCoherent); dev() is the device's view of it.
+enum class Mem { Device, Pinned, Mapped };
+// What reserve() does before it replaces a buffer: wait for the context's stream (work enqueued
+// there may still use the old one), or nothing (the caller knows that nothing does).
+enum class Wait { Stream, None };
+
+// An owning buffer of `cap()` elements.  Converts to T*, so pointer arithmetic and kernel arguments
+// read as with a raw pointer.
+template <class T, Mem K = Mem::Device>
+class Buf {
+public:
+    Buf() = default;
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    ~Buf() { (void)release(); }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    T* operator->() const { return p_; }
+    T* dev() const {
+        static_assert(K == Mem::Mapped, "only mapped memory has a device view");
+        return dev_;
+    }
+    size_t cap() const { return cap_; }
+    // Room for `elems` elements: at once if there is; otherwise waits as `wait` says, frees, and
+    // allocates max(elems, cap + cap / 2).  The contents are not kept.
+    int reserve(ie_ctx* c, size_t elems, Wait wait = Wait::Stream);
+
+private:
+    hipError_t release() {
+        hipError_t e = hipSuccess;
+        if (p_) e = K == Mem::Device ? hipFree(p_) : hipHostFree(p_);
+        p_ = dev_ = nullptr;
+        cap_ = 0;
+        return e;
+    }
+    T* p_ = nullptr;
+    T* dev_ = nullptr;
+    size_t cap_ = 0;
+};
+
+// An event / a stream the owner destroys.  create() is lazy: it does nothing once the handle exists.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    operator hipEvent_t() const { return e; }
+    int create(ie_ctx* c, unsigned flags = hipEventDefault);
+};
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+    operator hipStream_t() const { return s; }
+    int create(ie_ctx* c, unsigned flags);
+};
+}  // namespace iec
 
 struct ie_ctx {
     int device = 0;
-    hipStream_t own = nullptr;
+    // (the streams come first: members are destroyed last to first, so every buffer and event
+    // below is gone before the streams that used it)
+    iec::Stream own;
+    iec::Stream tab_stream;
     hipStream_t stream = nullptr;
     std::string err;
 
     int n = 0;
     uint16_t q[64] = {};
-    ie::EncTables* h_tab = nullptr;
-    ie::EncTables* d_tab = nullptr;
+    iec::Buf<ie::EncTables, iec::Mem::Pinned> h_tab;
+    iec::Buf<ie::EncTables> d_tab;
 
     // decoupled look-back state
-    uint64_t* d_state = nullptr;  // [kStateWordsPerTile * cap_tiles] tile chain granules (ie_common.hpp)
-    size_t cap_tiles = 0;
+    iec::Buf<uint64_t> d_state;   // [kStateWordsPerTile * state_tiles()] tile chain granules (ie_common.hpp)
+    size_t state_tiles() const { return d_state.cap() / size_t(ie::kStateWordsPerTile); }
     uint32_t tag = 0;
-    unsigned long long* d_ticket = nullptr;
+    iec::Buf<unsigned long long> d_ticket;
     unsigned long long ticket_base = 0;
 
-    uint64_t* d_frame_start = nullptr;  // [cap_frames]
-    uint64_t* d_chain_end = nullptr;    // [cap_frames]
-    size_t cap_frames = 0;
-    unsigned* d_err = nullptr;          // [kErrWords] counters that only grow
-    uint32_t* d_wave_fix = nullptr;     // [cap_tiles * waves per tile] fix-up requests of the last launch
+    iec::Buf<uint64_t> d_frame_start;   // [>= 64] grows with d_chain_end
+    iec::Buf<uint64_t> d_chain_end;
+    iec::Buf<unsigned> d_err;           // [kErrWords] counters that only grow
+    iec::Buf<uint32_t> d_wave_fix;      // [state_tiles() * waves per tile] fix-up requests of the last launch
     int last_fix_words = 0;
     unsigned err_seen[iec::kErrWords] = {};  // d_err's values at the previous read
     bool use_ticket = false;            // order tiles with an atomic ticket (after a timeout)
-    hipEvent_t stage_ev[4] = {};        // timing events around the last batched histogram [0,1] / pack [2,3]
+    iec::Event stage_ev[4];             // timing events around the last batched histogram [0,1] / pack [2,3]
     bool stage_rec[2] = {false, false};
     bool stage_timing = false;          // ie_set_stage_timing
     int fake_timeouts = 0;              // debug (IE_FAKE_TIMEOUTS): report this many look-back timeouts
@@ -70,127 +144,96 @@ struct ie_ctx {
     const char* async_what = nullptr;
 
     // staging for host-resident inputs / outputs
-    uint8_t* d_in = nullptr;
-    size_t cap_in = 0;
-    uint8_t* d_out = nullptr;
-    size_t cap_out = 0;
-    uint8_t* d_scratch = nullptr;   // quantize-only stream sink
-    size_t cap_scratch = 0;
-    int16_t* d_coef = nullptr;
-    size_t cap_coef = 0;
+    iec::Buf<uint8_t> d_in;
+    iec::Buf<uint8_t> d_out;
+    iec::Buf<uint8_t> d_scratch;    // quantize-only stream sink
+    iec::Buf<int16_t> d_coef;
 
     uint64_t last_fallbacks = 0;
 
     // Huffman tables / histogram
-    uint32_t* d_code = nullptr;        // [256] codes, then [256/4] packed lengths (one block)
-    uint32_t* h_code = nullptr;        // pinned mirror
-    uint32_t* d_hist = nullptr;        // [256]
+    iec::Buf<uint32_t> d_code;         // [256] codes, then [256/4] packed lengths (one block)
+    iec::Buf<uint32_t, iec::Mem::Pinned> h_code;  // pinned mirror
+    iec::Buf<uint32_t> d_hist;         // [256]
     // batched Huffman: device + pinned staging (hist/first of every string, then the pack tables)
-    uint8_t* d_batch = nullptr;
-    size_t cap_batch = 0;
-    uint8_t* h_batch = nullptr;
-    size_t cap_hbatch = 0;
+    iec::Buf<uint8_t> d_batch;
+    iec::Buf<uint8_t, iec::Mem::Pinned> h_batch;
     // pipelined batches: two pinned slots for the histogram read-back and two for the pack tables,
     // each guarded by an event (no stream-wide synchronisation between batches)
-    uint8_t* h_hist[2] = {};
-    size_t cap_hhist[2] = {};
-    hipEvent_t ev_hist[2] = {};
+    iec::Buf<uint8_t, iec::Mem::Pinned> h_hist[2];
+    iec::Event ev_hist[2];
     int hist_count[2] = {};
-    uint8_t* h_pack[2] = {};
-    size_t cap_hpack[2] = {};
-    hipEvent_t ev_pack[2] = {};    // the table copy out of pinned slot i (on tab_stream)
+    iec::Buf<uint8_t, iec::Mem::Pinned> h_pack[2];
+    iec::Event ev_pack[2];         // the table copy out of pinned slot i (on tab_stream)
     bool pack_recorded[2] = {};
-    uint8_t* d_pack[2] = {};       // device table slots
-    size_t cap_dpack[2] = {};
-    hipEvent_t ev_packed[2] = {};  // the pack (and prefix copies) that read device slot i
+    iec::Buf<uint8_t> d_pack[2];   // device table slots
+    iec::Event ev_packed[2];       // the pack (and prefix copies) that read device slot i
     bool packed_recorded[2] = {};
-    hipStream_t tab_stream = nullptr;
     int pack_slot = 0;
     int fused_count = 0;  // > 0: the last encode (ie_encode_images_counted) left this many histograms in d_chist
     // the counted pipeline: the encoder's histograms (cleared by the first-occurrence pass that reads
     // them: chist_zero_rows), and per pinned slot the device n / first / unresolved the rare first_full
     // pass of ie_huffman_hist_batch_wait needs, with the batch it reads
-    uint32_t* d_chist = nullptr;
-    size_t cap_chist = 0;  // (words)
+    iec::Buf<uint32_t> d_chist;
     // leading 256-word rows of d_chist known to be zero (the counted encode skips its memset when
     // its rows lie within them), and the rows that will be zero once the fused pass has read -- and
     // cleared -- the last counted encode's rows
     size_t chist_zero_rows = 0, chist_clean_after = 0;
     bool hist_skip_zero = false;  // one shot: encode() skips its histogram memset (set by the counted encode)
-    uint8_t* d_cslot[2] = {};
-    size_t cap_cslot[2] = {};
+    iec::Buf<uint8_t> d_cslot[2];
     bool hist_fused[2] = {};
     const uint8_t* hist_in[2] = {};
     size_t hist_pitch[2] = {};
     // decoder scratch
-    uint8_t* d_dec = nullptr;          // staged stream + padding
-    size_t cap_dec = 0;
+    iec::Buf<uint8_t> d_dec;           // staged stream + padding
     // 8-byte words.  Record decode: 32-bit arrays carved by dec_scratch (ie_capi_decode.cpp) -- the
     // chunks' record bases and counts, the count workgroups' totals, the top-level entries, the
     // speculative exits.  Huffman decode: [cap] chunk entries, [cap] symbol bases, 130 words of
     // top-level entries.
-    uint64_t* d_walk = nullptr;
-    size_t cap_walk = 0;
-    uint32_t* d_count = nullptr;       // Huffman decode: per-chunk symbol counts, then the walk workgroups' totals
-    size_t cap_count = 0;
-    uint16_t* d_rtab = nullptr;        // chunk transfer tables and the composites of every level (record and Huffman parse)
-    size_t cap_rtab = 0;
-    uint16_t* d_rpos = nullptr;        // record parse: record positions per chunk
-    size_t cap_rpos = 0;
+    iec::Buf<uint64_t> d_walk;
+    iec::Buf<uint32_t> d_count;        // Huffman decode: per-chunk symbol counts, then the walk workgroups' totals
+    iec::Buf<uint16_t> d_rtab;         // chunk transfer tables and the composites of every level (record and Huffman parse)
+    iec::Buf<uint16_t> d_rpos;         // record parse: record positions per chunk
     // [8].  Record decode: [1] compose tickets, [2] the speculative parse's fail flag, [3..7] walk
     // statistics (IE_PROFILE builds).  Huffman decode: [1] the changed / invalid flag pair, [2] the
     // symbol total, [5] its ticket.  ie_huffman_hist: [3] its ticket.
-    uint64_t* d_misc = nullptr;
-    uint64_t* h_decres = nullptr;      // record decode results, pinned host memory the device writes
-    uint64_t* d_decres = nullptr;      // directly ([0] end bit, [1] record total): no read-back copy
-    // ie_decode_images: [cap_imgres][2] the same pair per image, then [cap_imgres] the images'
-    // stream lengths on their way to d_imgbits (pinned, mapped: h_ / d_ are the two views)
-    uint64_t* h_imgres = nullptr;
-    uint64_t* d_imgres = nullptr;
-    size_t cap_imgres = 0;
-    uint64_t* d_imgbits = nullptr;     // [cap_imgbits] stream bits of every image (device)
-    size_t cap_imgbits = 0;
-    uint16_t* d_hlut = nullptr;        // Huffman decode prefix table (32768 entries)
-    size_t cap_hlut = 0;
-    uint8_t* d_hout = nullptr;         // Huffman decode output staging (host destinations)
-    size_t cap_hout = 0;
+    iec::Buf<uint64_t> d_misc;
+    // record decode results, pinned host memory the device writes directly through h_decres.dev()
+    // ([0] end bit, [1] record total): no read-back copy
+    iec::Buf<uint64_t, iec::Mem::Mapped> h_decres;
+    // ie_decode_images: [count][2] the same pair per image, then [count] the images' stream lengths
+    // on their way to d_imgbits (the device writes the pairs through h_imgres.dev())
+    iec::Buf<uint64_t, iec::Mem::Mapped> h_imgres;
+    iec::Buf<uint64_t> d_imgbits;      // stream bits of every image (device)
+    iec::Buf<uint16_t> d_hlut;         // Huffman decode prefix table (32768 entries)
+    iec::Buf<uint8_t> d_hout;          // Huffman decode output staging (host destinations)
     // ie_huffman_decode_batch.  d_hufb: the scratch of one sub-batch, per image and sized from the
     // longest stream, one array per kind holding every image's part in turn (HufScratch,
     // ie_capi_huffman.cpp).  d_hufb_res, 8-byte words for the whole batch: [n] stream bits, [n] first
     // code bits, [n] flag pairs (capacity, invalid code), [n] symbol totals; h_hufb_res: its pinned
     // mirror (the first two arrays go up, the last two come back in the call's one read).
-    uint8_t* d_hufb = nullptr;
-    size_t cap_hufb = 0;
-    uint64_t* d_hufb_res = nullptr;
-    size_t cap_hufb_res = 0;
-    uint8_t* h_hufb_res = nullptr;
-    size_t cap_hhufb_res = 0;
-    uint8_t* d_pix = nullptr;
-    size_t cap_pix = 0;
+    iec::Buf<uint8_t> d_hufb;
+    iec::Buf<uint64_t> d_hufb_res;
+    iec::Buf<uint8_t, iec::Mem::Pinned> h_hufb_res;
+    iec::Buf<uint8_t> d_pix;
     int last_chunks = 0;               // chunks of the last record decode
     int last_groups = 0;               // and their groups
     int last_spec = 0;                 // 1: the last record decode was the speculative parse
     int spec_parse = 0;                // ie_set_exact_parse(ctx, 0): speculative record parse first
     int spec_warm = 0;                 // ie_set_spec_warm(ctx, w): w warm-up chunks (<= 8)
-    unsigned long long* d_first = nullptr;  // [256]
+    iec::Buf<unsigned long long> d_first;   // [256]
     ie_pipe* pipe = nullptr;           // streamed host path of image batches (created on first use)
     // P-frame videos (ie_encode_gop): reconstructed frames (two, alternating), the prediction
     // error's coefficients and record lengths, the scan's tile sums, the frames' bit positions
-    uint8_t* d_gop_rec = nullptr;
-    size_t cap_gop_rec = 0;
-    int16_t* d_gop_coef = nullptr;
-    size_t cap_gop_coef = 0;
-    uint32_t* d_gop_bits = nullptr;
-    size_t cap_gop_bits = 0;
-    uint64_t* d_gop_tile = nullptr;
-    size_t cap_gop_tile = 0;
-    uint64_t* d_gop_pos = nullptr;
-    size_t cap_gop_pos = 0;
+    iec::Buf<uint8_t> d_gop_rec;
+    iec::Buf<int16_t> d_gop_coef;
+    iec::Buf<uint32_t> d_gop_bits;
+    iec::Buf<uint64_t> d_gop_tile;
+    iec::Buf<uint64_t> d_gop_pos;
     // ie_encode_gop_groups: one wave of groups' scratch, carved per kind (every group's slot, then
     // every group's reconstructed frames, coefficients, record lengths, tile sums; the wave's
     // position table and the groups' first bits).  The frames' positions in the stream: d_gop_pos.
-    uint8_t* d_gopg = nullptr;
-    size_t cap_gopg = 0;
+    iec::Buf<uint8_t> d_gopg;
 };
 
 namespace iec {
@@ -220,24 +263,39 @@ inline bool is_ptr_type(const void* p, hipMemoryType type) {
 inline bool is_device_ptr(const void* p) { return is_ptr_type(p, hipMemoryTypeDevice); }
 inline bool is_pinned_ptr(const void* p) { return is_ptr_type(p, hipMemoryTypeHost); }
 
-template <class T>
-int ensure(ie_ctx* c, T*& p, size_t& cap, size_t need_elems) {
-    if (cap >= need_elems && p) return IE_OK;
-    if (p) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(p));
-        p = nullptr;
+template <class T, Mem K>
+int Buf<T, K>::reserve(ie_ctx* c, size_t elems, Wait wait) {
+    if (p_ && cap_ >= elems) return IE_OK;
+    const size_t n = std::max(elems, cap_ + cap_ / 2);
+    if (p_) {
+        if (wait == Wait::Stream) HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, release());
     }
-    size_t n = std::max(need_elems, cap + cap / 2);
-    HIPCHK(c, hipMalloc(&p, n * sizeof(T)));
-    cap = n;
+    void* p = nullptr;
+    if (K == Mem::Device)
+        HIPCHK(c, hipMalloc(&p, n * sizeof(T)));
+    else
+        HIPCHK(c, hipHostMalloc(&p, n * sizeof(T),
+                                K == Mem::Mapped ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault));
+    p_ = static_cast<T*>(p);
+    if (K == Mem::Mapped) {  // (a failure here leaves cap() at 0: the next reserve starts over)
+        HIPCHK(c, hipHostGetDevicePointer(&p, p_, 0));
+        dev_ = static_cast<T*>(p);
+    }
+    cap_ = n;
     return IE_OK;
 }
 
-// pinned host staging (the stream is synchronised before an existing buffer is replaced)
-int ensure_pinned(ie_ctx* c, uint8_t*& p, size_t& cap, size_t need);
+inline int Event::create(ie_ctx* c, unsigned flags) {
+    if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, flags));
+    return IE_OK;
+}
+inline int Stream::create(ie_ctx* c, unsigned flags) {
+    if (!s) HIPCHK(c, hipStreamCreateWithFlags(&s, flags));
+    return IE_OK;
+}
 
-// The device's view of pinned host memory (mapped, or any hipHostMalloc under unified addressing).
+// The device's view of plain pinned host memory (any hipHostMalloc under unified addressing).
 template <class T>
 int device_view(ie_ctx* c, T* host, T** dev) {
     void* dp = nullptr;
