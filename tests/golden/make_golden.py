@@ -159,6 +159,15 @@ def cases():
         add(f"syn{gen}4k_4x4_huff", s4, 3840, 2160, 4, 1, "matrix.txt", True)
         sv2 = dict(kind="synth", gen=gen, w=1920, h=1080, frames=3, seed=S + 200, yuv420=True)
         add(f"vid{gen}1080x3_4x4", sv2, 1920, 1080, 4, 1, "matrix.txt", video=True)
+    # matrices that are not powers of two (tests/matrix_sweep.py: jpeg_like, annex_k, primes,
+    # ref_dc3, annex_k_div5).  The files are this project's own, not reference assets.
+    su200 = dict(kind="synth", gen="U", w=200, h=56, seed=S + 7)
+    su256 = dict(kind="synth", gen="U", w=256, h=256, seed=S)
+    add("ex6_4x4_jpeg", ex6, 512, 256, 4, 1, "matrix4_jpeg.txt", decode=True)
+    add("ex6_8x8_annexk", ex6, 512, 256, 8, 1, "matrix8_annexk.txt", decode=True)
+    add("synU200x56_4x4_primes", su200, 200, 56, 4, 1, "matrix4_primes.txt", decode=True)
+    add("synU200x56_4x4_dc3", su200, 200, 56, 4, 1, "matrix4_dc3.txt", decode=True)
+    add("synU256_8x8_annexk5", su256, 256, 256, 8, 1, "matrix8_annexk5.txt", decode=True)
     return out
 
 

@@ -112,6 +112,8 @@ def cases():
     add("gopP16x16x4_g4_m8", "P", 16, 16, 4, S + 120, 4, 8)
     add("gopflat128_16x16x4_g4_m8", "flat128", 16, 16, 4, S + 120, 4, 8)
     add("gopshiftA32x16x4_g4_m8", "shiftA", 32, 16, 4, S + 121, 4, 8)
+    # a matrix without powers of two (tests/matrix_sweep.py: jpeg_like)
+    add("gopP64x48x5_g3_m8_jpeg", "P", 64, 48, 5, S + 100, 3, 8, matrix="matrix4_jpeg.txt")
     return out
 
 

@@ -115,6 +115,7 @@ CLI_CASES = [c for c in O.manifest() if c["input"]["kind"] == "asset"]
 @pytest.mark.parametrize("c", CLI_CASES, ids=[c["name"] for c in CLI_CASES])
 def test_cli_encode_decode_golden(work, c):
     _put(os.path.join(O.GOLDEN, c["input"]["file"]), os.path.join(work, "in.raw"))
+    _put(os.path.join(O.GOLDEN, c["matrix"]), os.path.join(work, c["matrix"]))
     conf = _image_conf(work, width=c["w"], height=c["h"], rle=c["rle"], quantfile=c["matrix"])
     env = {"IE_BLOCKSIZE": str(c["n"])}
     enc_exe = _bin("encoder" if c["huffman"] else "encoder_nohuff")

@@ -7,6 +7,7 @@ compared with torch.equal; any difference is reported with its frame.  A time bu
 run; the summary (blocks compared, mismatches, FP64 fix-up requests) goes to a JSON file.
 
 usage: python tools/fuzz_exact.py --n 4 --blocks 1e9 --budget 600 --out profiles/r02_fuzz_4x4.json
+       (--matrix FILE: another quantisation matrix than the reference's matrix.txt / matrix8_1.txt)
 """
 import argparse
 import json
@@ -25,11 +26,12 @@ ap.add_argument("--n", type=int, default=4)
 ap.add_argument("--blocks", type=float, default=1e9)
 ap.add_argument("--budget", type=float, default=600.0, help="seconds")
 ap.add_argument("--batch", type=int, default=16)
+ap.add_argument("--matrix", default="", help="matrix file (a name under tests/golden or a path)")
 ap.add_argument("--out", default="")
 args = ap.parse_args()
 
 n, w, h, B = args.n, 3840, 2160, args.batch
-q = O.read_matrix("matrix.txt" if n == 4 else "matrix8_1.txt", n)
+q = O.read_matrix(args.matrix or ("matrix.txt" if n == 4 else "matrix8_1.txt"), n)
 codec = Codec(0, q, n)
 dev = "cuda"
 pitch = (stream_bound(w, h, n, 1, 0) + 255) // 256 * 256
@@ -93,7 +95,8 @@ while done < args.blocks and time.time() - t0 < args.budget:
     it += 1
     if it % 10 == 0:
         print(f"{done:.3e} blocks, {mism} mismatching frames, {time.time() - t0:.0f} s", flush=True)
-res = {"n": n, "blocks_compared": done, "target_blocks": args.blocks, "frames_mismatching": mism,
+res = {"n": n, **({"matrix": os.path.basename(args.matrix)} if args.matrix else {}), "blocks_compared": done,
+       "target_blocks": args.blocks, "frames_mismatching": mism,
        "mismatches": bad[:20], "per_kind_blocks": per_kind, "fp64_fixup_requests_fast": fix,
        "seconds": round(time.time() - t0, 1), "complete": done >= args.blocks,
        "method": "4K frames, FAST (FP32 + FP64 near-tie) vs EXACT (all FP64, reference order) streams "
