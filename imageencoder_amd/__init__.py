@@ -85,6 +85,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ie_last_end_bits.restype = C.c_void_p
     L.ie_last_fallbacks.argtypes = [vp, u64p]
     L.ie_quantize_frames.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp]
+    if hasattr(L, "ie_probe_sizes"):  # (absent from an older IE_LIB build under comparison)
+        L.ie_probe_sizes.restype = C.c_int
+        L.ie_probe_sizes.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, u16p, C.c_int,
+                                     u64p]
     for name in ("ie_huffman_hist", "ie_huffman_pack", "ie_bitcopy", "ie_decode_frames"):
         if hasattr(L, name):
             getattr(L, name).restype = C.c_int
@@ -153,6 +157,14 @@ def load_host_library(path: str | None = None) -> C.CDLL:
     vp, ip = C.c_void_p, C.POINTER(C.c_int)
     H.ieh_encode_image.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp,
                                    C.c_size_t]
+    if hasattr(H, "ieh_encode_image_budget"):  # (absent from an older IE_LIB build under comparison)
+        H.ieh_scale_matrix.restype = C.c_int
+        H.ieh_scale_matrix.argtypes = [vp, C.c_int, C.c_int, vp]
+        H.ieh_budget_ladder.restype = C.c_int
+        H.ieh_budget_ladder.argtypes = [ip]
+        H.ieh_encode_image_budget.restype = C.c_int64
+        H.ieh_encode_image_budget.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.c_size_t, vp, C.c_size_t, ip]
     H.ieh_encode_video.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, vp, C.c_size_t]
     H.ieh_encode_video_gop.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
@@ -225,6 +237,26 @@ def read_matrix(path: str, n: int) -> np.ndarray:
     if len(vals) != n * n or any(v <= 0 or v > 0xFFFF for v in vals):
         raise ValueError(f"{path}: expected {n * n} values in 1..65535, got {len(vals)}")
     return np.array(vals, dtype=np.uint16)
+
+
+def scale_matrix(base, percent: int) -> np.ndarray:
+    """``base`` (4x4 or 8x8) scaled to ``percent`` % (ieh_scale_matrix): every entry
+    ``clamp((v * percent + 50) // 100, 1, 65535)``, uint16, flat.  Raises on ``percent < 1``."""
+    H = load_host_library()
+    base = np.ascontiguousarray(np.asarray(base, dtype=np.uint16).ravel())
+    n = int(round(base.size ** 0.5))
+    out = np.zeros(base.size, dtype=np.uint16)
+    r = H.ieh_scale_matrix(base.ctypes.data, n, int(percent), out.ctypes.data)
+    if r != IE_OK:
+        raise IEError(r, f"scale_matrix: {n}x{n} matrix, percent {percent}")
+    return out
+
+
+def budget_ladder() -> list[int]:
+    """The 32 percents :meth:`Codec.encode_image_budget` probes first (ieh_budget_ladder)."""
+    H = load_host_library()
+    out = (C.c_int * 32)()
+    return list(out[: H.ieh_budget_ladder(out)])
 
 
 def stream_bound(w: int, h: int, n: int, nframes: int = 1, start_bit: int = 0) -> int:
@@ -452,6 +484,32 @@ class Codec:
                                             coef.ctypes.data))
         return coef
 
+    def probe_sizes(self, y, w: int, h: int, qs, nframes: int = 1, rle: bool = True, stride: int | None = None,
+                    frame_pitch: int | None = None, out=None) -> np.ndarray:
+        """The payload bits of every frame under every candidate matrix of ``qs`` (``(nq, n*n)``
+        or a list of matrices; at most 64) from one pass over the pixels (ie_probe_sizes): shape
+        ``(nq, nframes)`` uint64, entry ``[m, f]`` = the ``frame_bits[f]`` of :meth:`encode_frames`
+        after ``set_quant(qs[m])``.  The codec's own matrix is left as it was.  ``y``: numpy array
+        or torch tensor.  ``out``: an optional device tensor of ``nq * nframes`` 64-bit entries,
+        which receives the sums instead -- the call is then asynchronous and returns ``out``."""
+        stride = w if stride is None else stride
+        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        nn = (self.n or 0) ** 2
+        qs = np.ascontiguousarray(np.asarray(qs, dtype=np.uint16).reshape(-1, nn) if nn else
+                                  np.asarray(qs, dtype=np.uint16))
+        nq = qs.shape[0] if nn else 1
+        u64p = C.POINTER(C.c_uint64)
+        if out is not None:
+            if _nbytes(out) < 8 * nq * nframes:
+                raise IEError(IE_EINVAL, "probe_sizes: out holds fewer than nq * nframes 64-bit entries")
+            self._chk(self.L.ie_probe_sizes(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, int(rle),
+                                            qs.ctypes.data, nq, C.cast(C.c_void_p(_ptr(out)), u64p)))
+            return out
+        bits = np.zeros((max(nq, 1), nframes), dtype=np.uint64)
+        self._chk(self.L.ie_probe_sizes(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, int(rle), qs.ctypes.data,
+                                        nq, bits.ctypes.data_as(u64p)))
+        return bits
+
     def host_array(self, nbytes: int) -> np.ndarray:
         """A uint8 numpy array in page-locked host memory (ie_host_alloc): host buffers the
         streamed path DMAs directly.  Freed when the array (and the codec) are gone."""
@@ -562,6 +620,26 @@ class Codec:
         r = self._host_chk(H.ieh_encode_image(self.h, _ptr(y), w, h, q.ctypes.data, n, int(rle), int(huffman), mode,
                                               out.ctypes.data, cap))
         return out[:r].tobytes()
+
+    def encode_image_budget(self, y, w: int, h: int, q, n: int, budget: int, rle: bool = True, huffman: bool = True,
+                            mode: int = MODE_FAST):
+        """An image file with the finest probed scale of ``q`` whose size -- header + payload,
+        before the Huffman pass -- fits ``budget`` bytes (ieh_encode_image_budget): ``(bytes,
+        percent)``.  Raises ``IEError(IE_ECAP, ...)`` (``e.percent`` = 5382) when no scale fits.
+        The codec's matrix afterwards is the chosen one."""
+        H = load_host_library()
+        q = np.ascontiguousarray(np.asarray(q, dtype=np.uint16).ravel())
+        cap = stream_bound(w, h, n, 1, 2048) + 64
+        out = np.zeros(cap, dtype=np.uint8)
+        pc = C.c_int(0)
+        r = H.ieh_encode_image_budget(self.h, _ptr(y), w, h, q.ctypes.data, n, int(rle), int(huffman), mode,
+                                      int(budget), out.ctypes.data, cap, C.byref(pc))
+        if r < 0:
+            e = IEError(int(r), self.L.ie_last_error(self.h).decode())
+            e.percent = int(pc.value)
+            raise e
+        self.n = n
+        return out[: int(r)].tobytes(), int(pc.value)
 
     def encode_video_file(self, yuv, w: int, h: int, q, n: int, rle: bool = True, huffman: bool = True,
                           merange: int = 0, mode: int = MODE_FAST, gop: int = 1) -> bytes:

@@ -92,7 +92,8 @@ void write_header(util::BitStreamWriter& hdr, const FileParams& p) {
     }
 }
 
-int encode_file(ie_ctx* c, const uint8_t* y, const FileParams& p, std::vector<uint8_t>& out, std::string& err) {
+int encode_file(ie_ctx* c, const uint8_t* y, const FileParams& p, std::vector<uint8_t>& out, std::string& err,
+                size_t* pre_bytes) {
     if (!c) return (err = "no GPU context", IE_EHIP);
     int r;
     if ((r = ie_set_quant(c, p.q, p.n))) return (err = ie_last_error(c), r);
@@ -119,6 +120,7 @@ int encode_file(ie_ctx* c, const uint8_t* y, const FileParams& p, std::vector<ui
                                      s.enc.p, s.enc.cap, H, nullptr, &end)))
         return (err = ie_last_error(c), r);
     const size_t bytes = size_t((end + 7) / 8);
+    if (pre_bytes) *pre_bytes = bytes;
     if (!p.huffman) {
         out.resize(bytes);
         if ((r = ie_memcpy(c, out.data(), s.enc.p, bytes))) return (err = ie_last_error(c), r);
@@ -566,6 +568,130 @@ int64_t ieh_encode_image(ie_ctx* c, const uint8_t* y, int w, int h, const uint16
     const int r = dc::encode_file(c, y, p, v, err);
     if (r) return r;
     if (v.size() > cap) return IE_ECAP;
+    std::memcpy(out, v.data(), v.size());
+    return int64_t(v.size());
+}
+
+// ---- rate control: scale the matrix until the file fits a byte budget (ie_probe_sizes)
+namespace {
+// round(100 * 2^(j/4)), j = -8 .. 23: the scales the budget search probes first
+const int kBudgetLadder[32] = {25,  30,  35,  42,  50,  59,  71,   84,   100,  119,  141,  168,  200,  238,  283,  336,
+                               400, 476, 566, 673, 800, 951, 1131, 1345, 1600, 1903, 2263, 2691, 3200, 3805, 4525, 5382};
+
+// File bytes (before any Huffman pass) of every percent in `pc` for one frame: one ie_probe_sizes
+// call over the distinct scaled matrices.
+int budget_sizes(ie_ctx* c, const uint8_t* y, dc::FileParams p, const uint16_t* base, const std::vector<int>& pc,
+                 std::vector<uint64_t>& bytes) {
+    const int nn = p.n * p.n;
+    std::vector<uint16_t> qs;        // the distinct matrices, in order of first use
+    std::vector<int> which(pc.size());
+    std::vector<uint16_t> q(static_cast<size_t>(nn));
+    for (size_t i = 0; i < pc.size(); i++) {
+        ieh_scale_matrix(base, p.n, pc[i], q.data());
+        size_t m = 0;
+        for (; m * nn < qs.size(); m++)
+            if (std::equal(q.begin(), q.end(), qs.begin() + m * nn)) break;
+        if (m * nn == qs.size()) qs.insert(qs.end(), q.begin(), q.end());
+        which[i] = int(m);
+    }
+    const int nq = int(qs.size() / size_t(nn));
+    std::vector<uint64_t> bits(static_cast<size_t>(nq), 0);
+    const int r = ie_probe_sizes(c, y, p.w, p.h, size_t(p.w), 0, 1, p.rle ? 1 : 0, qs.data(), nq, bits.data());
+    if (r) return r;
+    bytes.resize(pc.size());
+    for (size_t i = 0; i < pc.size(); i++) {
+        p.q = qs.data() + size_t(which[i]) * nn;
+        util::BitStreamWriter hdr(64);
+        dc::write_header(hdr, p);  // (its length depends on the matrix's widest value)
+        bytes[i] = (uint64_t(hdr.get_position()) + bits[size_t(which[i])] + 7) / 8;
+    }
+    return IE_OK;
+}
+}  // namespace
+
+int ieh_budget_ladder(int* out) {
+    if (out) std::copy(kBudgetLadder, kBudgetLadder + 32, out);
+    return 32;
+}
+
+int ieh_scale_matrix(const uint16_t* base, int n, int percent, uint16_t* out) {
+    if (!base || !out || (n != 4 && n != 8) || percent < 1) return IE_EINVAL;
+    for (int k = 0; k < n * n; k++) {
+        const int64_t v = (int64_t(base[k]) * int64_t(percent) + 50) / 100;
+        out[k] = uint16_t(std::min<int64_t>(std::max<int64_t>(v, 1), 65535));
+    }
+    return IE_OK;
+}
+
+int64_t ieh_encode_image_budget(ie_ctx* c, const uint8_t* y, int w, int h, const uint16_t* base, int n, int rle,
+                                int huffman, int mode, size_t budget_bytes, uint8_t* out, size_t cap, int* percent) {
+    if (!c || !y || !base || !out || !percent || (n != 4 && n != 8)) return IE_EINVAL;
+    int r;
+    if ((r = ie_set_quant(c, base, n))) return r;  // the probe's block size and transform tables
+    dc::FileParams p;
+    p.w = w;
+    p.h = h;
+    p.n = n;
+    p.rle = rle != 0;
+    p.huffman = huffman != 0;
+    p.mode = mode;
+    // a host frame goes to the device once, for both probes and the encode
+    const uint8_t* dy = y;
+    if (!dc::is_device(c, y) && w > 0 && h > 0) {
+        dc::Scratch& s = dc::scratch(c);
+        const size_t px = size_t(w) * size_t(h);
+        if ((r = s.pix.reserve(px))) return r;
+        if ((r = ie_memcpy(c, s.pix.p, y, px))) return r;
+        dy = s.pix.p;
+    }
+    std::vector<int> ladder(kBudgetLadder, kBudgetLadder + 32);
+    std::vector<uint64_t> size;
+    if ((r = budget_sizes(c, dy, p, base, ladder, size))) return r;
+    int i1 = -1;  // the smallest ladder percent whose file fits
+    for (int i = 0; i < 32 && i1 < 0; i++)
+        if (size[size_t(i)] <= budget_bytes) i1 = i;
+    if (i1 < 0) {
+        *percent = kBudgetLadder[31];
+        ie_set_error(c, "no scale up to 5382 % meets the budget");
+        return IE_ECAP;
+    }
+    int best = kBudgetLadder[i1];
+    uint64_t best_bytes = size[size_t(i1)];
+    if (i1 > 0) {  // the integers between the two ladder entries, at most 32 of them
+        const int p0 = kBudgetLadder[i1 - 1], p1 = kBudgetLadder[i1];
+        std::vector<int> fine;
+        for (int i = 1; i <= 32; i++) {
+            const int v = p0 + (i * (p1 - p0) + 32) / 33;  // p0 + ceil(i (p1 - p0) / 33)
+            if (v > p0 && v < p1 && (fine.empty() || fine.back() != v)) fine.push_back(v);
+        }
+        if (!fine.empty()) {
+            std::vector<uint64_t> fsize;
+            if ((r = budget_sizes(c, dy, p, base, fine, fsize))) return r;
+            for (size_t i = 0; i < fine.size(); i++)
+                if (fsize[i] <= budget_bytes) {
+                    best = fine[i];
+                    best_bytes = fsize[i];
+                    break;
+                }
+        }
+    }
+    std::vector<uint16_t> q(static_cast<size_t>(n * n));
+    ieh_scale_matrix(base, n, best, q.data());
+    p.q = q.data();
+    std::vector<uint8_t> v;
+    std::string err;
+    size_t pre = 0;
+    if ((r = dc::encode_file(c, dy, p, v, err, &pre))) return r;
+    *percent = best;
+    if (uint64_t(pre) != best_bytes) {
+        ie_set_error(c, ("budget encode: the file is " + std::to_string(pre) + " bytes before the Huffman pass, the probe said " +
+                         std::to_string(best_bytes)).c_str());
+        return IE_EDEVICE;
+    }
+    if (v.size() > cap) {
+        ie_set_error(c, "output capacity below the encoded file");
+        return IE_ECAP;
+    }
     std::memcpy(out, v.data(), v.size());
     return int64_t(v.size());
 }

@@ -1,0 +1,77 @@
+// imageencoder_amd/csrc/ie_capi_probe.cpp -- ie_probe_sizes: the payload bits of a batch of frames
+// under many candidate quantisation matrices, from one pass over the pixels (ie_probe.hip).  It
+// reads the context's P / S tables (they depend on the block size only) and leaves its matrix,
+// tables, chain state and end bits alone.
+#include "ie_ctx.hpp"
+
+using namespace iec;
+
+namespace {
+// algo.cpp:68-87: natural index of zig-zag position z (the kernel's lanes are zig-zag positions)
+const uint8_t kZz4[16] = {0, 1, 4, 8, 5, 2, 3, 6, 9, 12, 13, 10, 7, 11, 14, 15};
+const uint8_t kZz8[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                          41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                          30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+}  // namespace
+
+extern "C" int ie_probe_sizes(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,
+                              int use_rle, const uint16_t* q, int nq, uint64_t* bits) {
+    if (!c || !y || !q || !bits) return IE_EINVAL;
+    int r = check_frames(c, w, h, nframes, stride, frame_pitch);
+    if (r) return r;
+    if (nq < 1 || nq > IE_PROBE_MAX)
+        return fail(c, IE_EINVAL, "nq must be in [1, " + std::to_string(int(IE_PROBE_MAX)) + "]");
+    const int n = c->n, nn = n * n;
+    for (int m = 0; m < nq; m++)
+        for (int k = 0; k < nn; k++)
+            if (q[size_t(m) * nn + k] == 0)
+                return fail(c, IE_EINVAL, "candidate matrix " + std::to_string(m) + " has a zero entry (entries must be > 0)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool in_dev = is_device_ptr(y), bits_dev = is_device_ptr(bits);
+    if (bits_dev && reinterpret_cast<uintptr_t>(bits) % 8) return fail(c, IE_EINVAL, "device bits must be 8-byte aligned");
+
+    const uint8_t* dy;
+    if ((r = stage_in(c, y, in_dev, frames_span(nframes, frame_pitch, stride, w, h), &dy))) return r;
+
+    // the candidates, zig-zag ordered, through pinned memory (an earlier call's copy out of it may
+    // still be in flight when the calls are asynchronous)
+    const size_t qcap = size_t(IE_PROBE_MAX) * 64;
+    if ((r = c->h_probe_q.reserve(c, qcap))) return r;
+    if ((r = c->d_probe_q.reserve(c, qcap))) return r;
+    if ((r = c->ev_probe.create(c, hipEventDisableTiming))) return r;
+    if (c->probe_recorded) HIPCHK(c, hipEventSynchronize(c->ev_probe));
+    const uint8_t* zz = n == 4 ? kZz4 : kZz8;
+    for (int m = 0; m < nq; m++)
+        for (int z = 0; z < nn; z++) c->h_probe_q[size_t(m) * nn + z] = q[size_t(m) * nn + zz[z]];
+    HIPCHK(c, hipMemcpyAsync(c->d_probe_q, c->h_probe_q, size_t(nq) * nn * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_probe, c->stream));
+    c->probe_recorded = true;
+
+    const size_t nsums = size_t(nq) * size_t(nframes);
+    uint64_t* dbits = bits;
+    if (!bits_dev) {
+        if ((r = c->d_probe_bits.reserve(c, nsums))) return r;
+        dbits = c->d_probe_bits;
+    }
+    HIPCHK(c, hipMemsetAsync(dbits, 0, nsums * sizeof(uint64_t), c->stream));
+
+    ie::ProbeArgs a{};
+    a.y = dy;
+    a.stride = stride;
+    a.frame_pitch = frame_pitch;
+    a.bx = w / n;
+    a.by = h / n;
+    a.nframes = nframes;
+    a.rle = use_rle ? 1 : 0;
+    a.vec_ok = (reinterpret_cast<uintptr_t>(dy) % 4 == 0 && stride % 4 == 0 && (nframes == 1 || frame_pitch % 4 == 0)) ? 1 : 0;
+    a.nq = nq;
+    a.q = c->d_probe_q;
+    a.tab = c->d_tab;
+    a.bits = reinterpret_cast<unsigned long long*>(dbits);
+    ie::launch_probe_sizes(a, n, c->stream);
+    HIPCHK(c, hipGetLastError());
+    if (bits_dev) return IE_OK;  // asynchronous on the context's stream
+    HIPCHK(c, hipMemcpyAsync(bits, dbits, nsums * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return IE_OK;
+}

@@ -124,6 +124,20 @@ int encode_small_tiles();             // a launch of fewer tiles does not fill t
 void launch_word_scatter(const uint32_t* src, uint32_t* dst, uint64_t pitch_words, int n, hipStream_t s);  // horizontally adjacent blocks per lane (Geo<N>::BPT)
 int encode_threads_per_tile();       // threads per encoder workgroup (= tile)
 
+// ie_probe_sizes (ie_probe.hip): the payload bits of every frame under nq candidate matrices.
+struct ProbeArgs {
+    const uint8_t* y;
+    uint64_t stride, frame_pitch;
+    int bx, by, nframes;
+    int rle;
+    int vec_ok;              // rows may be read with 4-byte loads
+    int nq;                  // 1 .. IE_PROBE_MAX
+    const uint16_t* q;       // [nq][N*N] candidates in ZIG-ZAG order (device)
+    const EncTables* tab;    // P and S of the block size (they do not depend on the matrix)
+    unsigned long long* bits;  // [nq][nframes], zero before the launch: bits[m * nframes + f] is added to
+};
+void launch_probe_sizes(const ProbeArgs& a, int n, hipStream_t s);
+
 struct PackArgs {            // Huffman re-encode / bit copy: one variable-length code per byte
     const uint8_t* in;
     uint64_t n;              // input bytes

@@ -168,6 +168,31 @@ int ie_quantize_frames(ie_ctx* ctx, const uint8_t* y, int w, int h, size_t strid
  * structural coefficient at a tie, one per block with another coefficient near a tie). */
 int ie_last_fallbacks(ie_ctx* ctx, uint64_t* count);
 
+/* "How big will this be?" -- the payload bits of every frame under nq candidate quantisation
+ * matrices, from ONE pass over the pixels and without writing a stream (rate control: the matrix
+ * travels in every file's header, so a file written with any matrix is a valid file).
+ *   y, w, h, stride, frame_pitch, nframes   as ie_encode_frames (y host or device memory); the same
+ *                checks with the same codes, IE_ENOQUANT before any ie_set_quant (the block size n
+ *                and the transform tables come from it)
+ *   q            host array of nq matrices, n*n uint16 each, row-major, n = the block size of the
+ *                last ie_set_quant
+ *   bits         nq * nframes entries, host or device (8-byte aligned) memory
+ * bits[m*nframes + f] equals the frame_bits[f] that ie_encode_frames returns for these frames after
+ * ie_set_quant(ctx, q + m*n*n, n), in either mode and for either use_rle: the unquantised
+ * coefficient is formed once in the reference's FP64 order (algo.cpp:314-325), every candidate
+ * divides (IEEE), rounds half away from zero and sizes the record by Block.cpp:186-232, :383-397.
+ *  - IE_EINVAL: nq < 1, nq > IE_PROBE_MAX, or a matrix entry equal to 0 (ie_last_error names the
+ *    matrix index).
+ *  - The context's own matrix, tables and ie_last_end_bits are left exactly as they were: an encode
+ *    after a probe equals the encode before it.
+ *  - With a device `bits` the call is asynchronous on the context's stream (bits is zeroed there,
+ *    the candidates go through pinned memory, then the launch).  With a host `bits` it
+ *    synchronises once and reads the sums back in one copy.  Host frames are staged through the
+ *    context's input buffer. */
+enum { IE_PROBE_MAX = 64 };
+int ie_probe_sizes(ie_ctx* ctx, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch,
+                   int nframes, int use_rle, const uint16_t* q, int nq, uint64_t* bits);
+
 /* ---- Device memory on the context's stream (for hosts that keep streams device-resident
  * between stages, e.g. the host library's encode -> Huffman pipeline).  ie_memcpy infers the
  * direction of each pointer and is asynchronous only when both are device memory. */

@@ -330,6 +330,33 @@ int64_t ieh_write_header(uint8_t* out, size_t cap, int n, const uint16_t* q, int
 // y: host or device; out: host.  Returns bytes written, < 0 on error.
 int64_t ieh_encode_image(ie_ctx* ctx, const uint8_t* y, int w, int h, const uint16_t* q, int n, int rle,
                          int huffman, int mode, uint8_t* out, size_t cap);
+// ---- Rate control by scaling the quantisation matrix (the matrix travels in the file's header, so
+// a file written with any matrix is a valid file for the reference decoder).
+// out[k] = clamp((base[k] * percent + 50) / 100, 1, 65535) in 64-bit integer arithmetic; percent >= 1
+// (IE_EINVAL otherwise, and for n not 4 or 8).  No GPU involved.
+int ieh_scale_matrix(const uint16_t* base, int n, int percent, uint16_t* out);
+// The 32 percents the budget search probes first: round(100 * 2^(j/4)), j = -8 .. 23 (25 .. 5382),
+// into out (optional).  Returns 32.
+int ieh_budget_ladder(int* out);
+// Whole image file (as ieh_encode_image writes it) with the FINEST probed scale of `base` whose
+// file fits budget_bytes.  Returns the bytes written, *percent = the scale chosen.
+//  - The size judged is ceil((header bits + payload bits) / 8) BEFORE any Huffman pass: the header
+//    as ieh_write_header writes it for the scaled matrix (its length depends on the matrix's widest
+//    value), the payload from ie_probe_sizes.  With huffman = 1 the chosen matrix then goes through
+//    the normal ieh_encode_image path and the file is whatever that yields: usually smaller, in the
+//    reference's "no gain" case (Huffman.cpp:329-341) those bytes plus one bit, so possibly one
+//    byte over the budget.
+//  - Size is not monotone in the scale (the matrix, the quotients and the header width are all
+//    rounded), so the search does not bisect: ONE ie_probe_sizes call over the ladder above (distinct
+//    matrices only); p1 = the smallest ladder percent that fits, p0 the entry below it; ONE more call
+//    over the integers p0 + ceil(i (p1 - p0) / 33), i = 1 .. 32, strictly between the two; the result
+//    is the smallest percent of both sets that fits.  p1 = 25 ends the search at once.
+//  - Nothing fits: IE_ECAP, *percent = 5382, nothing written, ie_last_error "no scale up to 5382 %
+//    meets the budget" (the context's matrix is then `base`).  Otherwise the context's matrix is the
+//    chosen one.  IE_ECAP with another message: cap is below the file.
+//  - IE_EDEVICE if the encoded file's size before the Huffman pass ever differs from the probed one.
+int64_t ieh_encode_image_budget(ie_ctx* ctx, const uint8_t* y, int w, int h, const uint16_t* base, int n, int rle,
+                                int huffman, int mode, size_t budget_bytes, uint8_t* out, size_t cap, int* percent);
 // gop=1 video file from a YUV420 buffer (frame_count = len / (1.5 w h)).
 int64_t ieh_encode_video(ie_ctx* ctx, const uint8_t* yuv, size_t len, int w, int h, const uint16_t* q, int n,
                          int rle, int huffman, int merange, int mode, uint8_t* out, size_t cap);
