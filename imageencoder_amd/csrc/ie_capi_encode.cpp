@@ -9,7 +9,7 @@ namespace iec {
 
 int launch_chain(ie_ctx* c, const Launch& L) {
     const int bpt = ie::encode_blocks_per_thread(c->n);
-    const Geometry g = geometry(L.w, L.h, c->n, L.nframes, bpt);
+    const Geometry g = geometry(L.w, L.h, c->n, L.nframes);
     // a launch too small to fill the chip: its tiles reach the look-back together (deep windows)
     const bool small = g.ntiles < ie::encode_small_tiles();
     const bool vec_ok = (reinterpret_cast<uintptr_t>(L.dy) % size_t(bpt * c->n) == 0) &&
@@ -71,7 +71,7 @@ int launch_chain(ie_ctx* c, const Launch& L) {
     }
     a.stamps = d_stamps;
     a.deep_lb = small ? 1 : 0;
-    const int fix_per_tile = ie::launch_encode(a, c->n, L.mode == IE_MODE_EXACT, c->stream, bpt);
+    const int fix_per_tile = ie::launch_encode(a, c->n, L.mode == IE_MODE_EXACT, c->stream);
     c->last_fix_words = (L.mode == IE_MODE_EXACT) ? 0 : g.ntiles * fix_per_tile;
     HIPCHK(c, hipGetLastError());
     if (d_stamps) {

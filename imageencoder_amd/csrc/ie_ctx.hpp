@@ -347,9 +347,9 @@ inline int mvec_bits(int merange) {
 struct Geometry {
     int bx, by, gpr, gpf, tpf, ntiles;
 };
-inline Geometry geometry(int w, int h, int n, int nframes, int bpt = 0) {
+inline Geometry geometry(int w, int h, int n, int nframes) {
     Geometry g;
-    if (!bpt) bpt = ie::encode_blocks_per_thread(n);
+    const int bpt = ie::encode_blocks_per_thread(n);
     g.bx = w / n;
     g.by = h / n;
     g.gpr = (g.bx + bpt - 1) / bpt;

@@ -1,5 +1,6 @@
 // imageencoder_amd/csrc/ie_device.h -- structures shared by the host context (ie_capi.cpp) and
-// the gfx950 kernels (ie_encode.hip, ie_huffman.hip, ie_decode.hip).
+// the gfx950 kernels (ie_encode.hip, ie_encode4p.hip, ie_huffman.hip, ie_decode.hip, ie_pframe.hip,
+// ie_probe.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -116,12 +117,13 @@ struct EncArgs {
 constexpr int kStamps = 64;  // encode_kernel: [0, 16) by thread 0; encode4p_kernel: [4 waves][16] by each wave's lane 0
 // chain-state words per tile (the host allocates; ie_common.hpp kGran must not exceed it)
 constexpr int kStateWordsPerTile = 16;
-// bpt: blocks per thread, encode_blocks_per_thread(n, ntiles at the default) for the launch
 // returns the FP64-statistics words per tile the launched kernel writes (EncArgs::wave_fix)
-int launch_encode(const EncArgs& a, int n, bool exact, hipStream_t s, int bpt);
-int encode_blocks_per_thread(int n);  // the batch default (4x4: 4, 8x8: 1)
+int launch_encode(const EncArgs& a, int n, bool exact, hipStream_t s);
+// the wave-local 4x4 FAST encoder (ie_encode4p.hip); launch_encode checks its preconditions
+int launch_encode4p(const EncArgs& a, hipStream_t s);
+int encode_blocks_per_thread(int n);  // horizontally adjacent blocks per lane, Geo<N>::BPT (4x4: 4, 8x8: 1)
 int encode_small_tiles();             // a launch of fewer tiles does not fill the chip (deep look-back)
-void launch_word_scatter(const uint32_t* src, uint32_t* dst, uint64_t pitch_words, int n, hipStream_t s);  // horizontally adjacent blocks per lane (Geo<N>::BPT)
+void launch_word_scatter(const uint32_t* src, uint32_t* dst, uint64_t pitch_words, int n, hipStream_t s);
 int encode_threads_per_tile();       // threads per encoder workgroup (= tile)
 
 // ie_probe_sizes (ie_probe.hip): the payload bits of every frame under nq candidate matrices.

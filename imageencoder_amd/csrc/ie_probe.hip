@@ -1,9 +1,9 @@
 // imageencoder_amd/csrc/ie_probe.hip -- ie_probe_sizes on gfx950: the payload bits of every frame
 // under many candidate quantisation matrices, in one pass over the pixels.
 //
-// The unquantised coefficient D = acc * S[k] of the exact path (exact_coef_inl, ie_encode.hip) does
+// The unquantised coefficient D = acc * S[k] of the exact path (exact_coef_inl, ie_encode_blocks.h) does
 // not depend on the matrix; only round(D / q) does, and a record's length follows from the rounded
-// values alone (size_block, ie_encode.hip; size4 / rec_len, ie_pframe.hip).  So D is formed once
+// values alone (size_block, ie_encode_blocks.h; size4 / rec_len, ie_pframe.hip).  So D is formed once
 // per coefficient, in FP64 in the reference's operation order (this file is compiled with
 // -ffp-contract=off), and every candidate divides, rounds and sizes from it.  No stream is written
 // and no look-back chain exists: the lengths are summed.

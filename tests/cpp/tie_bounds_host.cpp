@@ -12,7 +12,7 @@
 //   bound     |t32 - t64| <= the bound the tables claim (thr/2; (1/2 - lim4j)/2, plus the 2^-27 that
 //             rounding lim4j to a float can hide; the tighter of dlo4h and 1 - dhi4h, halved); a
 //             dc_exact* coefficient matches exactly
-//   decision  where the kernel's flag rule (ie_encode.hip: the rounding residual against lim,
+//   decision  where the kernel's flag rule (ie_encode_blocks.h: the rounding residual against lim,
 //             lim4j; fract(t + 1/2) against dlo4h/dhi4h) does not flag a coefficient, the FP32
 //             rounding equals std::round of the FP64 quotient
 //   size      the block's record, bl and Lw as the reference sizes them (Block.cpp:186-232,
@@ -46,7 +46,7 @@ struct IntOp {
     int sub(int a, int b) const { return a - b; }
 };
 
-constexpr float kMagic = 12582912.0f;  // 1.5 * 2^23 (ie_encode.hip)
+constexpr float kMagic = 12582912.0f;  // 1.5 * 2^23 (ie_encode_blocks.h)
 constexpr int kDump = 1024;            // blocks of every kind written for the oracle comparison
 
 uint64_t rng_state;

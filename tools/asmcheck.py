@@ -123,8 +123,8 @@ def static_lds(path):
 # change that makes the compiler spill or drop a wave shows up in the CPU build, not only on a GPU
 # (an unguarded profiling branch once took the 8x8 kernel from 68 to 308 B of scratch, 2x slower).
 BUDGETS = {
-    "_ZN2ie13encode_kernelILi4ELb0ELb0ELi4EEEvNS_7EncArgsEPKNS_9EncTablesE": (5, 0),
-    "_ZN2ie13encode_kernelILi8ELb0ELb0ELi1EEEvNS_7EncArgsEPKNS_9EncTablesE": (4, 0),
+    "_ZN2ie13encode_kernelILi4ELb0ELb0EEEvNS_7EncArgsEPKNS_9EncTablesE": (5, 0),
+    "_ZN2ie13encode_kernelILi8ELb0ELb0EEEvNS_7EncArgsEPKNS_9EncTablesE": (4, 0),
     "_ZN2ie15encode4p_kernelILb0ELb0EEEvNS_7EncArgsEPKNS_9EncTablesE": (6, 0),
     "_ZN2ie15encode4p_kernelILb1ELb0EEEvNS_7EncArgsEPKNS_9EncTablesE": (6, 0),
     "_ZN2ie15encode4p_kernelILb0ELb1EEEvNS_7EncArgsEPKNS_9EncTablesE": (6, 0),
