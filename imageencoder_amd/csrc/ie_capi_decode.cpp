@@ -466,9 +466,11 @@ int ie_decode_gop(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bit, 
     RecPlan pl{};
     ie::RecParseArgs pa{};
     // (gop > 1: the plan is sized by the I-frame bound, but a P-frame's records are a few bits each
-    // -- at most kRecPosCap records per chunk (5 bits each at least with RLE: 4 header bits and
-    // one value bit) keeps its chunks on the listed-positions decode instead of the re-walk)
-    const uint64_t min_rec = use_rle ? 5u : uint64_t(4 + n * n);
+    // -- at most kRecPosCap records per chunk keeps its chunks on the listed-positions decode
+    // instead of the re-walk.  With RLE the shortest record is bl = 0: its 4 header bits alone.
+    // Without RLE the bound is the shortest record an encoder writes, bl = 1 (the 4-bit bl = 0
+    // record is valid there too; chunks dense with them take the re-walk))
+    const uint64_t min_rec = use_rle ? 4u : uint64_t(4 + n * n);
     const uint64_t cmax = (gop > 1 && IE_GOP_CAPC) ? uint64_t(ie::kRecPosCap) * min_rec : kMaxChunkBits;
     if ((r = plan_chunks(c, rec_bound, nblocks, cmax, &pl))) return r;
     if ((r = dec_scratch(c, pl, 1, pa))) return r;

@@ -6,8 +6,9 @@
 //                 entry position, record by record (length = 4 + bl*(rle + Lw) or 4 + bl*N*N),
 //                 and reports where it leaves the chunk.  The first walk starts every chunk at its
 //                 first bit (speculative); a record header that cannot occur in a real stream
-//                 (bl = 0, Lw > N*N) makes the walk slide one bit, so wrong walks quickly fall onto
-//                 the true record boundaries.  Fix-up rounds re-walk every chunk whose entry differs
+//                 (Lw > N*N) makes the walk slide one bit, so wrong walks quickly fall onto
+//                 the true record boundaries.  (bl = 0 is a record: 4 bits, a block of zeros --
+//                 the reference reads its count and values with get(0) = 0, BitStream.cpp:30-40.)  Fix-up rounds re-walk every chunk whose entry differs
 //                 from its predecessor's exit until nothing changes; then chunk 0's exact entry
 //                 (start_bit) makes every chunk exact by induction.
 //   index_kernel  the final walks write the start bit of every record (block index = exclusive scan
@@ -186,13 +187,13 @@ __device__ __forceinline__ uint32_t lbits(const uint32_t* L, uint32_t p, int l) 
 }
 
 // length of the record whose 20 header bits (bl:4, then the RLE length's bl bits) are `head`; 1
-// if no record can start there (a walk slides one bit; never on the true path of a well-formed
-// stream)
+// if no record can start there -- a count beyond the block -- (a walk slides one bit; never on
+// the true path of a well-formed stream).  bl = 0 is a record of 4 bits: no count bits, no values.
 template <int N>
 __device__ __forceinline__ uint32_t rec_len_head(uint32_t head, int rle) {
     constexpr int NN = N * N;
     const uint32_t bl = head >> 16;
-    if (!bl) return 1u;
+    if (!bl) return 4u;
     if (!rle) return 4u + bl * NN;
     const uint32_t lw = (head & 0xFFFFu) >> (16 - bl);
     return lw <= uint32_t(NN) ? 4u + bl * (lw + 1u) : 1u;
@@ -202,8 +203,8 @@ template <int N>
 __device__ __forceinline__ uint32_t rec_len_sel(uint32_t head, int rle) {
     constexpr uint32_t NN = N * N;
     const uint32_t bl = head >> 16;
-    const uint32_t lw = rle ? ((head & 0xFFFFu) >> (16u - bl)) : NN - 1u;  // (bl = 0: shifted out)
-    return (bl != 0u && lw <= NN) ? 4u + bl * (lw + 1u) : 1u;
+    const uint32_t lw = rle ? ((head & 0xFFFFu) >> (16u - bl)) : NN - 1u;  // (bl = 0: shifted out, lw = 0)
+    return lw <= NN ? 4u + bl * (lw + 1u) : 1u;                            // (bl = 0: 4 bits)
 }
 // length of the record at p, 0 if no record can start there
 template <int N>

@@ -1,8 +1,9 @@
 // ie_recbits.h -- which bit positions of a record stream can start a record, 32 positions at once.
 //
 // A record (Block::streamEncoded / loadFromStream, Block.cpp:406-472) opens with 4 bits bl, then --
-// with RLE -- the value count Lw in bl bits; the parse accepts a header when bl != 0 and Lw <= N*N
-// (rec_len_head in ie_decode.hip).  valid_mask32 evaluates that test for the 32 headers that
+// with RLE -- the value count Lw in bl bits; the parse accepts a header when Lw <= N*N
+// (rec_len_head in ie_decode.hip; bl = 0 has no count bits and no values: a record of 4 bits, so
+// without RLE every position can start a record).  valid_mask32 evaluates that test for the 32 headers that
 // start at positions p0 .. p0+31 of a 64-bit MSB-first window `v` (bit 63 = position p0; a
 // header needs at most 4 + 15 = 19 bits, so position p0+31 still fits) with bitwise operations
 // on shifted copies of the window: X_k holds, in bit (31 - q), the bit at position p0 + q + k.
@@ -37,12 +38,10 @@ IE_HD uint32_t valid_mask32(uint64_t v, int rle) {
     uint32_t X[19];
 #pragma unroll
     for (int k = 0; k < 19; k++) X[k] = uint32_t((v << k) >> 32);
-    const uint32_t nz = X[0] | X[1] | X[2] | X[3];  // bl != 0
-    if (!rle) return ie_bitrev32(nz);
-    // bl in [1, S]: any count fits.  S = 4: bl < 8 and bl != 0, minus 5..7 (0101, 0110, 0111):
-    // X0 = 0 and (X1 = 0 or X2 = X3 = 0).  S = 6: bl < 8 minus 7, or... (bl <= 6): X0 = 0 and not
-    // (X1 & X2 & X3).
-    uint32_t ok = (S == 4) ? (~X[0] & (~X[1] | ~(X[2] | X[3])) & nz) : (~X[0] & ~(X[1] & X[2] & X[3]) & nz);
+    if (!rle) return 0xFFFFFFFFu;
+    // bl in [0, S]: any count fits.  S = 4: bl < 8 minus 5..7 (0101, 0110, 0111): X0 = 0 and
+    // (X1 = 0 or X2 = X3 = 0).  S = 6: bl < 8 minus 7 (bl <= 6): X0 = 0 and not (X1 & X2 & X3).
+    uint32_t ok = (S == 4) ? (~X[0] & (~X[1] | ~(X[2] | X[3]))) : (~X[0] & ~(X[1] & X[2] & X[3]));
     uint32_t orTop = 0;  // X4 | ... | X(3 + t - 1): the count's top bits before bit t
 #pragma unroll
     for (int b = S + 1; b <= 15; b++) {

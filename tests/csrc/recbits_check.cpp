@@ -1,5 +1,5 @@
 // valid_mask32 (imageencoder_amd/csrc/ie_recbits.h) against the per-position header test
-// (rec_len_head, ie_decode.hip: bl != 0 and, with RLE, the bl-bit count <= N*N), on random,
+// (rec_len_head, ie_decode.hip: with RLE the bl-bit count <= N*N; bl = 0 is a 4-bit record), on random,
 // sparse and dense 64-bit windows, both block sizes, RLE on and off.
 #include <cstdio>
 #include <random>
@@ -10,8 +10,7 @@ template <int N>
 static bool head_ok(uint64_t v, int q, int rle) {
     const uint32_t head = uint32_t((v << q) >> 44);  // 20 bits from position q
     const uint32_t bl = head >> 16;
-    if (!bl) return false;
-    if (!rle) return true;
+    if (!bl || !rle) return true;
     const uint32_t lw = (head & 0xFFFFu) >> (16 - bl);
     return lw <= uint32_t(N * N);
 }

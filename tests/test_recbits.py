@@ -1,6 +1,6 @@
 """The decoder's 32-positions-at-once header test (imageencoder_amd/csrc/ie_recbits.h,
 valid_mask32) against the per-position test of the record parse (ie_decode.hip rec_len_head:
-bl != 0 and, with RLE, the bl-bit value count <= N*N, Block.cpp:442-472): every 20-bit header
+with RLE the bl-bit value count <= N*N, Block.cpp:442-472; bl = 0 is a 4-bit record): every 20-bit header
 and 2 M random / sparse / dense windows, 4x4 and 8x8, RLE on and off (tests/csrc/recbits_check.cpp)."""
 import os
 import subprocess
