@@ -77,24 +77,16 @@ int plan_chunks(ie_ctx* c, uint64_t span, uint64_t nblocks, uint64_t cmax, RecPl
     // 24) so that every chunk's walks are short; C a multiple of 32, at least
     // 256 bits, at most 2^15 (16-bit record positions; a table wave's LDS -- the chunk's bits and
     // valid-header bitmap -- stays small)
-    const int G = ie::rec_group_chunks(n);
     static const char* rs = getenv("IE_DEC_R");
     const uint64_t recs = rs ? std::max<uint64_t>(1, strtoull(rs, nullptr, 10)) : (n == 4 ? 24 : 28);
     const uint64_t want = std::max<uint64_t>((nblocks + recs - 1) / recs, 1);
     uint64_t C = (span + want - 1) / want;
     C = std::min<uint64_t>(std::max<uint64_t>((C + 31) / 32 * 32, 256), std::max<uint64_t>(cmax / 32 * 32, 256));
     const uint64_t nch = std::max<uint64_t>((span + C - 1) / C, 1);
-    // levels: ceil(n / G) composites per level until at most G remain (G^4 chunks at most)
-    size_t tab_rows = 0;
+    // levels: ceil(n / G) composites per level until at most G remain (kRecMaxLevels levels at
+    // most), counted by the code that launches them
     int levels = 0;
-    for (uint64_t cur = nch;; cur = (cur + G - 1) / G) {
-        tab_rows += cur;
-        levels++;
-        if ((cur + G - 1) / G <= uint64_t(G)) {
-            tab_rows += (cur + G - 1) / G;
-            break;
-        }
-    }
+    const size_t tab_rows = ie::rec_table_rows(size_t(nch), n, &levels);
     if (levels > ie::kRecMaxLevels || nch > uint64_t(INT32_MAX))
         return fail(c, IE_EINVAL, "stream too long for one decode call");
     *plan = {C, int(nch), tab_rows, levels};
@@ -143,7 +135,6 @@ int dec_scratch(ie_ctx* c, const RecPlan& pl, size_t batch, ie::RecParseArgs& a,
     a.wgsum = u32 + wg_at;
     a.E = u32 + e_at;
     if (spec) *spec = u32 + spec_at;
-    a.ticket = reinterpret_cast<unsigned*>(c->d_misc + 1);
     a.img_tab = s.img_tab;
     a.img_chunks = uint32_t(nch);
     a.img_wg = uint32_t(s.nwg);
@@ -152,8 +143,8 @@ int dec_scratch(ie_ctx* c, const RecPlan& pl, size_t batch, ie::RecParseArgs& a,
 }
 
 // Profiling of the single-stream record decode (IE_PROFILE builds, tools/prof_decode.py and
-// tools/dec_stamps.py): host-side phase times, the table pass's walk statistics (IE_DEC_STATS) and
-// per-wave stamps (IE_DEC_STAMPS = file: [table waves][8] u64 per call).  Empty in the product.
+// tools/dec_stamps.py): host-side phase times and the table pass's per-wave stamps (IE_DEC_STAMPS =
+// file: [table waves][8] u64 per call).  Empty in the product.
 #if IE_PROFILE
 struct DecHostTimes {
     double pre = 0, launch = 0, sync = 0;
@@ -169,15 +160,10 @@ struct DecProfile {
         return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
     }
     double t0 = now(), t1 = 0, t2 = 0;
-    const bool stats = getenv("IE_DEC_STATS") != nullptr;
     const char* stamps = getenv("IE_DEC_STAMPS");
     Buf<uint64_t> d_ws;
     size_t nws = 0;
     int begin(ie_ctx* c, ie::RecParseArgs& pa) {  // before the first launch
-        if (stats) {
-            pa.stats = reinterpret_cast<unsigned long long*>(c->d_misc + 3);  // [3..7]
-            HIPCHK(c, hipMemsetAsync(c->d_misc + 3, 0, 5 * sizeof(uint64_t), c->stream));
-        }
         int tm = 1, hb = 0;
         ie::rec_table_geometry(pa.C, c->n, &tm, &hb);
         nws = size_t(pa.nchunks + tm - 1) / size_t(tm) * 8;
@@ -190,20 +176,11 @@ struct DecProfile {
         return IE_OK;
     }
     void launched() { t2 = now(); }  // after the speculative attempt, before the exact parse
-    int end(ie_ctx* c, const ie::RecParseArgs& pa) {  // after the synchronisation
+    int end(ie_ctx* c, const ie::RecParseArgs&) {  // after the synchronisation
         g_dht.pre += t1 - t0;
         g_dht.launch += t2 - t1;
         g_dht.sync += now() - t2;
         g_dht.n++;
-        const int nchunks = pa.nchunks;
-        if (stats) {
-            uint64_t st[5];
-            HIPCHK(c, hipMemcpy(st, c->d_misc + 3, sizeof(st), hipMemcpyDeviceToHost));
-            fprintf(stderr, "[dec] chunks %d C %u: lane-steps %.1f/chunk, beyond-window %.1f/chunk, unmerged walks %.2f/chunk, "
-                    "wave max steps avg %.1f max %llu\n", nchunks, unsigned(pa.C), double(st[0]) / nchunks, double(st[1]) / nchunks,
-                    double(st[2]) / nchunks, double(st[3]) / nchunks, (unsigned long long)st[4]);
-            HIPCHK(c, hipMemsetAsync(c->d_misc + 3, 0, sizeof(uint64_t), c->stream));
-        }
         if (d_ws) {
             std::vector<uint64_t> hws(nws);
             HIPCHK(c, hipMemcpy(hws.data(), d_ws, nws * 8, hipMemcpyDeviceToHost));

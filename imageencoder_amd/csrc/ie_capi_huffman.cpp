@@ -706,18 +706,18 @@ int ie_huffman_decode(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_b
     const size_t cap = (c->d_walk.cap() - 130) / 2;
     unsigned* flags = reinterpret_cast<unsigned*>(c->d_misc + 1);
     uint32_t* E = reinterpret_cast<uint32_t*>(wk + 2 * cap);
-    unsigned* ticket = reinterpret_cast<unsigned*>(c->d_misc + 5);
+    // (the flag pair and the total are words [1] and [2]; 48 bytes, a multiple of 16, because a
+    // 24-byte fill measured 3 us slower per call: profiles/decode_split_isa.txt)
     HIPCHK(c, hipMemsetAsync(c->d_misc, 0, 6 * sizeof(uint64_t), c->stream));
     const uint32_t* W = reinterpret_cast<const uint32_t*>(src);
-    const int rounds = ie::huffman_decode_device(W, nbits, start_bit, dlut, chunk_bits, wk, c->d_rtab, E, ticket,
-                                                 c->d_count, wk + cap, flags, c->d_misc + 2, nullptr, false,
-                                                 c->stream);
+    const int rounds = ie::huffman_decode_device(W, nbits, start_bit, dlut, chunk_bits, wk, c->d_rtab, E, c->d_count,
+                                                 wk + cap, flags, c->d_misc + 2, nullptr, false, c->stream);
     if (rounds < 0) return fail(c, IE_EHIP, "Huffman decode walk failed");
     HIPCHK(c, hipGetLastError());
     if (is_device_ptr(out)) {
         // device output: the emit follows at once, bounded by out_cap (a symbol past it is not
         // written and flags the launch), and the total and flags come back in ONE read
-        ie::huffman_decode_device(W, nbits, start_bit, dlut, chunk_bits, wk, c->d_rtab, E, ticket, c->d_count,
+        ie::huffman_decode_device(W, nbits, start_bit, dlut, chunk_bits, wk, c->d_rtab, E, c->d_count,
                                   wk + cap, flags, c->d_misc + 2, out, true, c->stream, uint64_t(out_cap));
         HIPCHK(c, hipGetLastError());
         uint64_t rb[2] = {0, 0};  // d_misc[1]: the two flag words, d_misc[2]: the total
@@ -736,7 +736,7 @@ int ie_huffman_decode(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_b
     // (a host destination from here on: the symbols are emitted into d_hout)
     if ((r = c->d_hout.reserve(c, size_t(total) + 1))) return r;
     uint8_t* dout = c->d_hout;
-    ie::huffman_decode_device(W, nbits, start_bit, dlut, chunk_bits, wk, c->d_rtab, E, ticket, c->d_count,
+    ie::huffman_decode_device(W, nbits, start_bit, dlut, chunk_bits, wk, c->d_rtab, E, c->d_count,
                               wk + cap, flags, c->d_misc + 2, dout, true, c->stream);
     HIPCHK(c, hipGetLastError());
     unsigned f[2] = {0, 0};

@@ -24,8 +24,7 @@
 #include "ie_device.h"
 
 // Profiling knobs exist only in IE_PROFILE builds (tools/variants.sh): the product library never
-// reads IE_ABLATE / IE_STAMPS / IE_DEC_STATS / IE_DEC_STAMPS, so no environment variable can change
-// its output.  IE_ABLATE_FORCE: A/B builds of an ablation.
+// reads IE_ABLATE / IE_STAMPS / IE_DEC_STAMPS, so no environment variable can change its output.  IE_ABLATE_FORCE: A/B builds of an ablation.
 #ifndef IE_PROFILE
 #define IE_PROFILE 0
 #endif
@@ -194,9 +193,9 @@ struct ie_ctx {
     iec::Buf<uint32_t> d_count;        // Huffman decode: per-chunk symbol counts, then the walk workgroups' totals
     iec::Buf<uint16_t> d_rtab;         // chunk transfer tables and the composites of every level (record and Huffman parse)
     iec::Buf<uint16_t> d_rpos;         // record parse: record positions per chunk
-    // [8].  Record decode: [1] compose tickets, [2] the speculative parse's fail flag, [3..7] walk
-    // statistics (IE_PROFILE builds).  Huffman decode: [1] the changed / invalid flag pair, [2] the
-    // symbol total, [5] its ticket.  ie_huffman_hist: [3] its ticket.
+    // [8].  Record decode: [2] the speculative parse's fail flag.  Huffman decode: [1] the changed /
+    // invalid flag pair, [2] the symbol total.  ie_huffman_hist: [3] its unresolved-bytes word.
+    // ([0] and [4..7] are unused, and [1] by the record decode.)
     iec::Buf<uint64_t> d_misc;
     // record decode results, pinned host memory the device writes directly through h_decres.dev()
     // ([0] end bit, [1] record total): no read-back copy

@@ -1,30 +1,33 @@
-// imageencoder_amd/csrc/ie_decode.hip -- the inverse path on gfx950 (ImageDecoder.cpp:55-122).
+// imageencoder_amd/csrc/ie_decode.hip -- the record parse and decode on gfx950, the inverse path
+// (ImageDecoder.cpp:55-122).
 //
-// The reference parses block records serially (Block::loadFromStream, Block.cpp:442-472) because
-// a record's length is only known once its header is read.  Here the parse is made parallel:
-//   walk_kernel   the stream is cut into fixed chunks of bits; one lane walks each chunk from an
-//                 entry position, record by record (length = 4 + bl*(rle + Lw) or 4 + bl*N*N),
-//                 and reports where it leaves the chunk.  The first walk starts every chunk at its
-//                 first bit (speculative); a record header that cannot occur in a real stream
-//                 (Lw > N*N) makes the walk slide one bit, so wrong walks quickly fall onto
-//                 the true record boundaries.  (bl = 0 is a record: 4 bits, a block of zeros --
-//                 the reference reads its count and values with get(0) = 0, BitStream.cpp:30-40.)  Fix-up rounds re-walk every chunk whose entry differs
-//                 from its predecessor's exit until nothing changes; then chunk 0's exact entry
-//                 (start_bit) makes every chunk exact by induction.
-//   index_kernel  the final walks write the start bit of every record (block index = exclusive scan
-//                 of per-chunk record counts).
-//   decode_kernel one lane per block: read bl / Lw / values, sign-extend (utils.hpp:265-269), place
-//                 them in zig-zag order, dequantise (Block.cpp:163-169), inverse DCT in the
-//                 reference's FP64 order (algo.cpp:343-363), +128, clamp and truncate to uint8
-//                 (Block.cpp:100-107).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+// The reference parses block records serially (Block::loadFromStream, Block.cpp:442-472) because a
+// record's length is only known once its header is read (4 + bl * (Lw + 1) bits with RLE, 4 +
+// bl * N * N without; bl = 0 is a record of 4 bits, a block of zeros -- the reference reads its
+// count and values with get(0) = 0, BitStream.cpp:30-40).  Here the stream is cut into chunks and
+// parsed exactly with the transfer tables of ie_decode_blocks.h: D = the longest record, 4 + 15 *
+// (N * N + 1) bits, and G = 32 tables per group (RecGeom, ie_device.h).
+//   rec_table2_kernel  a wave per tm chunks writes their transfer tables: the D walks of a chunk
+//                      share their work through claims in LDS -- the first walk to reach a position
+//                      owns it, a later walk that lands there stops and takes the owner's exit --
+//                      so about one walk per chunk survives.
+//   compose_kernel, compose_top_kernel (ie_decode_blocks.h) compose the tables.
+//   rec_count_kernel   a lane per chunk: entry = the prefix maps applied to its top-level entry;
+//                      the chunk's true records are walked from it: their positions and their
+//                      count; the workgroup scans its chunks' counts and stores their total.
+//   rec_decode_kernel  a wave per kDecChunks chunks: first block index = the totals of the count
+//                      workgroups before the chunk's, plus the counts before it in its own; a
+//                      record per lane: dequantise (Block.cpp:163-169), FP64 IDCT in the
+//                      reference's order (algo.cpp:343-363), +128, clamp, truncate
+//                      (Block.cpp:100-107).
+//   rec_spec_kernel    the optional speculative parse in place of tables and composition: a lane
+//                      per chunk walks from a warm-up distance before it; the count pass verifies
+//                      every exit and the decode writes nothing if one was wrong.
+//   gop_init_kernel    the position and total arrays of a device-chained video decode.
 #include <algorithm>
 #include <cstdlib>
 
-#include "ie_common.hpp"
-#include "ie_device.h"
+#include "ie_decode_blocks.h"
 #include "ie_recbits.h"
 
 namespace ie {
@@ -36,146 +39,6 @@ constexpr int kZZ8[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11
                           35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
                           58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 }  // namespace
-
-// bits [p, p+l) of the stream, l <= 32
-__device__ __forceinline__ uint32_t getbits(const uint32_t* W, uint64_t p, int l) {
-    if (l == 0) return 0;
-    const uint64_t w = p >> 5;
-    const uint64_t v = (uint64_t(bswap32(W[w])) << 32) | bswap32(W[w + 1]);
-    return uint32_t((v << (p & 31)) >> (64 - l));
-}
-
-// ---- Huffman decode (Huffman.cpp:354-402; the per-bit tree walk of :190-204) -------------------
-// One lane per chunk of bits decodes symbols with a prefix table until it leaves the chunk; its
-// entry comes from composed transfer tables (the exact parse at the end of this file); a scan of
-// the per-chunk symbol counts places every chunk's output; a last walk writes the symbols.  The
-// reference walks to the end of the buffer, padding bits of the last byte included (a code may run
-// past it with zero bits), and so does this walk.
-//   lut   [2^15]: sym | len << 8 for every 15-bit prefix, len 0 = no code (codes are <= 15 bits:
-//         the dictionary stores lengths in 4 bits, Huffman.cpp:41-42)
-//   LDS   the 2^kHufL1 first-level entries (codes of <= kHufL1 bits resolve there)
-constexpr int kHufL1 = 11;
-constexpr int kHufD = 15;   // entry offsets of a chunk: codes are at most 15 bits
-#ifndef IE_HUF_G
-#define IE_HUF_G 256
-#endif
-constexpr int kHufG = IE_HUF_G;  // tables per composition group
-struct HufArgs {
-    const uint32_t* words;
-    uint64_t nbits, start_bit, chunk_bits;
-    int nchunks;
-    const uint16_t* lut;
-    uint64_t* entry;
-    uint32_t* count;
-    uint32_t* wgsum;    // [walk workgroups] their chunks' symbol totals
-    unsigned* changed;  // [1] invalid code on the emitting walk; [0] output past out_cap (not written)
-    uint64_t* base;     // symbols before each chunk within its walk workgroup
-    uint8_t* out;
-    uint16_t* lvl[kRecMaxLevels];  // mode 2: the composition's levels
-    int levels;
-    const uint32_t* E;
-    uint64_t out_cap;   // bytes of out (the emit launched before the total is known checks it)
-    // image batch (the kernels' B instantiations; huf_image): the strides between the images' parts
-    size_t img_words;           // stream words
-    const uint64_t* img_nbits;  // [images] stream bits
-    const uint64_t* img_start;  // [images] first bit of the code stream
-    size_t img_tab;             // table entries (tables, composites, counts, middles)
-    uint32_t img_chunks, img_wg, img_E;
-    size_t out_pitch;           // bytes between the images' output slots (out_cap: bytes of a slot)
-};
-
-// Image batch: the launch's arguments rebased to image blockIdx.y -- its stream, its length, its
-// first bit (the dictionaries differ in length, so every image's chunk grid has its own phase),
-// its prefix table, its scratch, its flag pair and its output slot -- so that every pass below runs
-// on it as on a single stream.  One chunk plan serves the batch (nchunks from the longest stream):
-// a chunk past its image's stream holds no code.  (lvl[] is left alone: see huf_count_kernel.)
-template <bool B>
-__device__ __forceinline__ void huf_image(HufArgs& a) {
-    if constexpr (B) {
-        const size_t y = blockIdx.y;
-        a.words += y * a.img_words;
-        a.nbits = a.img_nbits[y];
-        a.start_bit = a.img_start[y];
-        a.lut += y << 15;
-        a.entry += y * a.img_chunks;
-        a.count += y * a.img_chunks;
-        a.base += y * a.img_chunks;
-        a.wgsum += y * a.img_wg;
-        a.changed += 2 * y;
-        a.E += y * a.img_E;
-        a.out += y * a.out_pitch;
-    }
-}
-
-__device__ __forceinline__ void huf_l1(const uint16_t* lut, uint16_t* l1) {
-    constexpr int B = 8;  // loads in flight per thread
-    for (int q0 = 0; q0 < (1 << kHufL1); q0 += B * int(blockDim.x)) {
-        uint16_t e[B];
-#pragma unroll
-        for (int u = 0; u < B; u++) {
-            const int q = q0 + u * int(blockDim.x) + int(threadIdx.x);
-            e[u] = q < (1 << kHufL1) ? lut[uint32_t(q) << (15 - kHufL1)] : uint16_t(0);
-        }
-#pragma unroll
-        for (int u = 0; u < B; u++) {
-            const int q = q0 + u * int(blockDim.x) + int(threadIdx.x);
-            if (q < (1 << kHufL1)) l1[q] = ((e[u] >> 8) != 0 && (e[u] >> 8) <= kHufL1) ? e[u] : uint16_t(0);  // 0: look in lut
-        }
-    }
-    __syncthreads();
-}
-
-// The symbols before workgroup g's chunks: the totals of the workgroups before it, summed by the
-// whole workgroup (every thread receives it).
-__device__ __forceinline__ uint64_t huf_wg_prefix(const uint32_t* wgsum, int g, uint32_t* scratch) {
-    uint64_t part = 0;
-    for (int i = threadIdx.x; i < g; i += kTPB) part += wgsum[i];
-    const uint64_t w = wave_sum64(part);
-    if ((threadIdx.x & 63) == 0) reinterpret_cast<uint64_t*>(scratch)[threadIdx.x >> 6] = w;
-    __syncthreads();
-    const uint64_t* s64 = reinterpret_cast<const uint64_t*>(scratch);
-    return s64[0] + s64[1] + s64[2] + s64[3];
-}
-
-// total receives the symbol count (device, 1 word): the sum of the walk's workgroup totals.
-// B (image batch): blockIdx.y = the image, its totals img_wg words after the previous image's.
-template <bool B = false>
-__global__ __launch_bounds__(kTPB) void huf_total_kernel(const uint32_t* wgsum, int nwg, uint64_t* total,
-                                                         uint32_t img_wg) {
-    __shared__ alignas(8) uint32_t scratch[8];
-    if constexpr (B) {
-        wgsum += size_t(blockIdx.y) * img_wg;
-        total += blockIdx.y;
-    }
-    const uint64_t t = huf_wg_prefix(wgsum, nwg, scratch);
-    if (threadIdx.x == 0) *total = t;
-}
-
-// ---- exact record parse: transfer tables, composed -------------------------------------------
-// A record's length depends on its own header, so the stream is a serial chain.  Cut it into
-// chunks of C bits.  The first record starting at or after a chunk's first bit sits at an offset
-// d < D (D = the longest record, 4 + 15*(N*N+1) bits: the record straddling the boundary ends
-// within D bits).  So a chunk is a FUNCTION of d: walking from offset d gives the offset at which
-// the walk enters the next chunk -- its transfer table T_k[d] over all D entries.  Tables compose
-// (T_{k+1} o T_k), and the true entry of every chunk follows from the stream's start by composing
-// tables: exact for any content, with no speculation to converge (periodic streams, which lock
-// speculative walks into a wrong phase, cost nothing extra).
-//   rec_table2_kernel  the D walks of a chunk share their work through claims in LDS -- the first
-//                      walk to reach a position owns it, a later walk that lands there stops and
-//                      takes the owner's exit -- so about one walk per chunk survives.
-//   rec_compose_kernel one workgroup per group of G tables: the group's tables in LDS, every entry
-//                      chased through them; the chase writes the group-relative prefix map P_j
-//                      over each table (group entry -> entry of table j) and the group's
-//                      composite.  Levels repeat on the composites until at most G remain; the
-//                      last workgroup of that level chases the stream's start through them.
-//   rec_count_kernel   one wave per chunk: entry = the prefix maps applied to its top-level entry;
-//                      the chunk's true records are walked from it: their positions, their count,
-//                      and the count added to a sum per 256 chunks.
-//   rec_decode_kernel  one wave per chunk: first block index = the sums before the chunk's 256,
-//                      plus the counts before it among them (one load per lane, a wave sum); the
-//                      lanes decode the records: dequantise (Block.cpp:163-169), FP64 IDCT in the
-//                      reference's order (algo.cpp:343-363), +128, clamp, truncate
-//                      (Block.cpp:100-107).
 
 constexpr uint32_t kRoot = 0x8000u;  // table pass: a walk result that is an exit, not an owner
 
@@ -222,54 +85,6 @@ __host__ __device__ constexpr int rec_count_wave_words(uint32_t C, int seg) {
 }
 int rec_count_seg(uint32_t C) {  // chunks per count wave: <= 16, a wave's bits within 10 KB
     return int(std::max<uint64_t>(1, std::min<uint64_t>(16, (uint64_t(10 * 1024) * 8 - 256) / C)));
-}
-
-
-// The stream word w (byte-swapped to MSB-first) with its bits at or past nbits cleared: the last
-// word may be read in place from a caller's buffer, whose bytes past the stream are not zero.
-__device__ __forceinline__ uint32_t tail_word(uint32_t raw, uint64_t w, uint64_t nbits) {
-    const uint32_t b = bswap32(raw);
-    const uint64_t vb = nbits - (w << 5);  // valid bits of this word (>= 1)
-    return vb >= 32 ? b : (b & ~(0xFFFFFFFFu >> uint32_t(vb)));
-}
-
-// Words [w0, w0 + nw) of the stream, byte-swapped to MSB-first, zeros past the stream's nbits,
-// with one pad word after every 32 (word i at i + i / 32): lanes walking chunks of
-// 1 024 bits side by side read words 32 apart -- one bank -- without it (lbits_pad reads it)
-__device__ __forceinline__ void stage_words_pad(uint32_t* L, const uint32_t* W, uint64_t w0, int nw, uint64_t nbits,
-                                                int tid, int nthreads) {
-    const uint64_t nwords = (nbits + 31) >> 5;
-    constexpr int B = 8;
-    for (int i0 = 0; i0 < nw; i0 += B * nthreads) {
-        uint32_t v[B];
-#pragma unroll
-        for (int u = 0; u < B; u++) {
-            const int i = i0 + u * nthreads + tid;
-            const uint64_t w = w0 + i;
-            if (i < nw && (w + 1) * 32 <= nbits) {
-                v[u] = __builtin_nontemporal_load(W + w);
-            } else if (i < nw && w < nwords) {  // the stream's last, partial word: its bytes only (the
-                                                // caller's buffer may end there)
-                const uint8_t* b = reinterpret_cast<const uint8_t*>(W + w);
-                uint32_t x = 0;
-                for (uint32_t e = 0; e < 4u && 32 * w + 8 * e < nbits; e++) x |= uint32_t(b[e]) << (8 * e);
-                v[u] = x;
-            } else {
-                v[u] = 0u;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < B; u++) {
-            const int i = i0 + u * nthreads + tid;
-            if (i < nw) L[i + (i >> 5)] = (w0 + i < nwords) ? tail_word(v[u], w0 + i, nbits) : 0u;
-        }
-    }
-}
-__host__ __device__ constexpr int pad_words(int nw) { return nw + (nw >> 5) + 1; }
-__device__ __forceinline__ uint32_t lbits_pad(const uint32_t* L, uint32_t p, int l) {
-    const uint32_t w = p >> 5, w1 = w + 1u, s = p & 31u;
-    const uint64_t v = (uint64_t(L[w + (w >> 5)]) << 32) | L[w1 + (w1 >> 5)];
-    return l ? uint32_t((v << s) >> (64 - l)) : 0u;
 }
 
 // zig-zag rank of every coefficient position (the inverse of kZZ4 / kZZ8)
@@ -348,149 +163,6 @@ __device__ __forceinline__ uint32_t decode_record(const uint32_t* L, uint32_t p,
         }
     }
     return p + uint32_t(length * bl);
-}
-
-// One composition level over n tables ([n][D], 16-bit exits): prefix maps written over the
-// tables, composites into comp ([ceil(n/G)][D]).  Shared by the record parse (D = the longest
-// record) and the Huffman decode (D = the longest code).
-// n 16-bit entries from global memory into LDS, 16 bytes per load where both sides allow it
-// (eight 16-byte loads per thread in flight before their LDS stores: one load-to-store round trip
-// per 32 KiB instead of one per 4 KiB)
-__device__ __forceinline__ void stage_u16(uint16_t* S, const uint16_t* T, int n, int tid) {
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    int head = 0;
-    if (((reinterpret_cast<uintptr_t>(T) | reinterpret_cast<uintptr_t>(S)) & 15u) == 0) {
-        head = n & ~7;
-        const int nv = head / 8;
-        const u4* src = reinterpret_cast<const u4*>(T);
-        u4* dst = reinterpret_cast<u4*>(S);
-        for (int i0 = 0; i0 < nv; i0 += 8 * kTPB) {
-            u4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int i = i0 + u * kTPB + tid;
-                if (i < nv) v[u] = src[i];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int i = i0 + u * kTPB + tid;
-                if (i < nv) dst[i] = v[u];
-            }
-        }
-    }
-    for (int i = head + tid; i < n; i += kTPB) S[i] = T[i];
-}
-
-// B (image batch): blockIdx.y = the image, whose tables and composites lie img entries after the
-// previous image's.
-template <int D, int G, bool B = false>
-__global__ __launch_bounds__(kTPB) void compose_kernel(uint16_t* tab, int n, uint16_t* comp, size_t img) {
-    __shared__ __attribute__((aligned(16))) uint16_t S[G * D];
-    const int tid = threadIdx.x, g = blockIdx.x;
-    if constexpr (B) {
-        tab += size_t(blockIdx.y) * img;
-        comp += size_t(blockIdx.y) * img;
-    }
-    const int k0 = g * G, nk = min(G, n - k0);
-    uint16_t* T = tab + size_t(k0) * D;
-    stage_u16(S, T, nk * D, tid);
-    __syncthreads();
-    // every entry chased through the group's tables; a thread's entries (tid, tid + kTPB, ...) are
-    // chased side by side, so their dependent LDS reads overlap
-    constexpr int CH = (D + kTPB - 1) / kTPB;
-    uint32_t x[CH];
-#pragma unroll
-    for (int c = 0; c < CH; c++) x[c] = uint32_t(tid + c * kTPB);
-    for (int j = 0; j < nk; j++) {
-#pragma unroll
-        for (int c = 0; c < CH; c++) {
-            const int d = tid + c * kTPB;
-            if (d < D) {
-                T[j * D + d] = uint16_t(x[c]);  // P_j: group entry d -> entry of table j
-                x[c] = S[j * D + x[c]];
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < CH; c++) {
-        const int d = tid + c * kTPB;
-        if (d < D) comp[size_t(g) * D + d] = uint16_t(x[c]);
-    }
-}
-
-// The top chase: the stream's start (entry 0) through the ng <= G top-level composites, E[q] = the
-// entry of composite q (one workgroup; a launch of its own, so the composites are visible without
-// a device-wide fence in every composing workgroup).  (A segmented chase -- every entry through
-// each of 8 segments, then entry 0 through the segment maps -- measured slower here and in
-// compose_kernel: 9.2 -> 11.6 and 15.2 -> 18.1 us.)
-template <int D, int G, bool B = false>
-__global__ __launch_bounds__(kTPB) void compose_top_kernel(const uint16_t* comp, int ng, uint32_t* E, size_t img,
-                                                           uint32_t img_E) {
-    __shared__ __attribute__((aligned(16))) uint16_t S[G * D];
-    if constexpr (B) {  // (every image's stream starts at its own first record: entry 0)
-        comp += size_t(blockIdx.y) * img;
-        E += size_t(blockIdx.y) * img_E;
-    }
-    stage_u16(S, comp, ng * D, threadIdx.x);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t x = 0;
-        for (int q = 0; q < ng; q++) {
-            E[q] = x;
-            x = S[q * D + x];
-        }
-    }
-}
-
-// The composition levels over n tables: level l+1's tables are level l's composites, until at
-// most G remain (the top chase).  lvl[l] receives level l's table array; returns the number of
-// levels, or -1 past kRecMaxLevels.  B: `images` batches of n tables each, img entries (E: img_E
-// words) apart, composed by the same launches (lvl[] receives image 0's arrays).
-template <int D, int G, bool B = false>
-int launch_compose(uint16_t* tab, int n, uint32_t* E, unsigned* ticket, uint16_t** lvl, hipStream_t s, int images = 1,
-                   size_t img = 0, uint32_t img_E = 0) {
-    int cur = n, levels = 0;
-    uint16_t* arr = tab;
-    for (;;) {
-        const int ng = (cur + G - 1) / G;
-        const int top = ng <= G ? 1 : 0;
-        if (levels >= kRecMaxLevels) return -1;
-        lvl[levels] = arr;
-        uint16_t* comp = arr + size_t(cur) * D;
-        hipLaunchKernelGGL((compose_kernel<D, G, B>), dim3(ng, images), dim3(kTPB), 0, s, arr, cur, comp, img);
-        levels++;
-        if (top) {
-            hipLaunchKernelGGL((compose_top_kernel<D, G, B>), dim3(1, images), dim3(kTPB), 0, s, comp, ng, E, img, img_E);
-            (void)ticket;
-            return levels;
-        }
-        arr = comp;
-        cur = ng;
-    }
-}
-
-// Table rows a composition over n tables needs (the tables and every level's composites).
-template <int D, int G>
-size_t compose_rows(int n) {
-    size_t rows = 0;
-    for (int cur = n;; cur = (cur + G - 1) / G) {
-        rows += size_t(cur);
-        if ((cur + G - 1) / G <= G) return rows + size_t((cur + G - 1) / G);
-    }
-}
-
-// the entry offset of table k: its top-level entry, then the prefix maps of every level down
-template <int D, int G>
-__device__ __forceinline__ uint32_t table_entry(const uint32_t* E, uint16_t* const* lvl, int levels, int k) {
-    int u = k;
-    for (int l = 0; l < levels; l++) u /= G;
-    uint32_t x = E[u];
-    for (int l = levels - 1; l >= 0; l--) {
-        int ul = k;
-        for (int m = 0; m < l; m++) ul /= G;
-        x = lvl[l][size_t(ul) * D + x];
-    }
-    return x;
 }
 
 // the chunk's entry offset (record parse): composed tables, or the predecessor's speculative exit
@@ -592,8 +264,9 @@ __device__ __forceinline__ int stage_words16(uint32_t* L, const uint32_t* W, uin
     return off;
 }
 
-// Table pass, round 3: one wave tabulates tm consecutive chunks (runtime, rec_table_geometry) and
-// walks only from positions where a record can start.  Entry d of a chunk first slides to the next
+// Table pass (rec_table2_kernel, below): one wave tabulates tm consecutive chunks (runtime,
+// rec_table_geometry) and walks only from positions where a record can start.  Entry d of a chunk
+// first slides to the next
 // valid position nv(d) -- every entry between two valid positions shares one walk -- so the walks
 // start at the valid positions of [0, min(D, C)) plus, for the entries past the last of them, the
 // first valid position after (v*, entry slot D of the chunk).  The walk list is compacted from the
@@ -603,6 +276,7 @@ __device__ __forceinline__ int stage_words16(uint32_t* L, const uint32_t* W, uin
 // chunk's end).  Results: a walk that merged takes its owner's exit (owner chains are read-only
 // chases; only non-roots are written).  The valid-header bitmap comes 32 positions at a time from
 // bitwise operations on shifted windows (valid_mask32, ie_recbits.h).
+
 // The first valid position at or after p before ce (ce: a chunk end, a multiple of 32), else ce.
 // NZ[i]: the first bitmap word at or after word i holding a valid position (a sentinel past the
 // last), so a run of positions where no record can start costs one read, not one per word.
@@ -1053,6 +727,10 @@ __global__ __launch_bounds__(64 * kRecWPB) void rec_decode_kernel(RecParseArgs a
 
 int rec_group_chunks(int n) { return n == 4 ? RecGeom<4>::G : RecGeom<8>::G; }
 int rec_entry_span(int n) { return n == 4 ? RecGeom<4>::D : RecGeom<8>::D; }
+size_t rec_table_rows(size_t nchunks, int n, int* levels) {
+    return n == 4 ? compose_rows<RecGeom<4>::D, RecGeom<4>::G>(nchunks, levels)
+                  : compose_rows<RecGeom<8>::D, RecGeom<8>::G>(nchunks, levels);
+}
 // chunks per table wave and claim slots: tm chunks' positions fit the 16-bit claim keys.  The
 // claim table is small on purpose (lossy, direct-mapped): measured on 4K streams, the occupancy a
 // small LDS footprint buys beats the merges a larger table finds (IE_REC_TM / IE_REC_HB override)
@@ -1079,8 +757,8 @@ int launch_rec_parse_decode_t(RecParseArgs a, const DecArgs& d, int images, hipS
     const int nt2 = (a.nchunks + a.tm - 1) / a.tm;
     const size_t l2 = size_t(rec_table2_words(a.C, RecGeom<N>::D, a.tm, a.hbits)) * 4;
     hipLaunchKernelGGL((rec_table2_kernel<N, B>), dim3(nt2, images), dim3(64), l2, s, a);
-    const int levels = launch_compose<RecGeom<N>::D, RecGeom<N>::G, B>(a.tab, a.nchunks, a.E, a.ticket + 1, a.lvl, s, images,
-                                                                       a.img_tab, a.img_E);
+    const int levels = launch_compose<RecGeom<N>::D, RecGeom<N>::G, B>(a.tab, a.nchunks, a.E, a.lvl, s, images, a.img_tab,
+                                                                       a.img_E);
     if (levels < 0) return -1;
     a.levels = levels;
     const int nbc = (a.nchunks + 4 * a.seg - 1) / (4 * a.seg);
@@ -1122,388 +800,6 @@ void launch_rec_spec_decode(const RecParseArgs& a, const DecArgs& d, int n, hipS
         hipLaunchKernelGGL((rec_count_kernel<8>), dim3(nbc), dim3(kTPB), lc, s, a);
         hipLaunchKernelGGL((rec_decode_kernel<8>), dim3(nb), dim3(64 * kRecWPB), rec_decode_lds(a.C, 8), s, a, d);
     }
-}
-
-// ---- exact Huffman parse: the same transfer tables --------------------------------------------
-// A code is at most 15 bits long, so the first code that starts at or after a chunk's first bit
-// sits at an offset d < 15: a chunk of the Huffman stream is a function of d exactly like a chunk
-// of the record stream, with 15 entries instead of D.  huf_table_kernel walks all 15 entries of
-// kHufTC chunks per workgroup (the chunks' bits staged in LDS; a position where no code
-// starts slides one bit -- never on the true path of a valid stream); compose_kernel composes the
-// tables; huf_count_kernel reads each chunk's symbol count at its true entry, and huf_emit_kernel
-// writes the symbols.  Exact for any content: a periodic stream (e.g. a
-// flat image's records, Huffman-coded) no longer leaves speculative walks locked in a wrong phase.
-// Walks from different entries of a chunk fall onto the same code boundaries after a few codes
-// (prefix codes resynchronise), so only the first kHufSync bits are walked from all 15 entries: the
-// walks that stand on the same first boundary at or past cs + kHufSync have merged; one walk per
-// distinct boundary (almost always one per chunk) goes on to the chunk's end, the workgroup's
-// survivors side by side.  Every entry also gets its symbol count to the exit (cnt), so the true
-// path's counts follow from the composed entries without another walk (huf_count_kernel).
-#ifndef IE_HUF_SYNC
-#define IE_HUF_SYNC 64
-#endif
-constexpr uint32_t kHufSync = IE_HUF_SYNC;
-#ifndef IE_HUF_TC
-#define IE_HUF_TC 64
-#endif
-constexpr int kHufTC = IE_HUF_TC;  // chunks per table workgroup: its survivors fill a wave
-// B (image batch): blockIdx.y = the image (huf_image), its table arrays img_tab entries after the
-// previous image's.  A workgroup whose chunks all lie past its image's stream walks nothing and
-// writes the rows those walks would end in: every entry leaves at the next chunk's first bit with
-// no code counted, the middle boundary at the chunk's end.
-template <bool B = false>
-__global__ __launch_bounds__(kTPB) void huf_table_kernel(HufArgs a, uint16_t* tab, uint16_t* cnt, uint16_t* mo,
-                                                          uint16_t* mc) {
-    constexpr int S = kHufTC * 16, U = S / kTPB;  // walk slots (chunk, entry); slots per thread
-    static_assert(S % kTPB == 0, "whole slots per thread");
-    __shared__ uint16_t l1[1 << kHufL1];
-    __shared__ uint32_t P[S], X[S], R[S + 1];  // boundary after the sync walk; exit; survivors
-    __shared__ uint16_t K2[S];                 // a survivor's codes from P to its exit
-    __shared__ uint32_t M[S];                  // its first boundary at or past the chunk's middle
-    __shared__ uint16_t KM[S];                 // its codes from P to that boundary
-    extern __shared__ uint32_t L[];            // the workgroup's chunks' bits (+ 64 past the last)
-    const int tid = threadIdx.x;
-    huf_image<B>(a);
-    if constexpr (B) {
-        const size_t img = size_t(blockIdx.y) * a.img_tab;
-        tab += img;
-        cnt += img;
-        mo += img;
-        mc += img;
-    }
-    if (tid == 0) R[S] = 0u;
-    const int k0 = blockIdx.x * kHufTC;
-    const uint32_t C = uint32_t(a.chunk_bits);
-    const int m = min(kHufTC, a.nchunks - k0);
-    const uint64_t c0 = a.start_bit + uint64_t(k0) * C;
-    if constexpr (B) {
-        if (c0 >= a.nbits) {
-            for (int i = tid; i < m * kHufD; i += kTPB) {
-                const size_t r = size_t(k0) * kHufD + i;
-                tab[r] = 0;
-                cnt[r] = 0;
-                mo[r] = uint16_t(C);
-                mc[r] = 0;
-            }
-            return;
-        }
-    }
-    const uint64_t base = c0 & ~31ull;
-    const uint32_t s0 = uint32_t(c0 - base);
-    stage_words_pad(L, a.words, base >> 5, int((s0 + uint32_t(m) * C + 64) >> 5) + 2, a.nbits, tid, kTPB);
-    huf_l1(a.lut, l1);  // (ends with a barrier: L staged too)
-    const uint32_t lim = uint32_t(min<uint64_t>(a.nbits - base, uint64_t(s0) + uint64_t(m) * C));
-    // one step from p: the next position (a code at p: counted in *n); past the stream: the
-    // chunk's end e (the last chunk's exit is never used)
-    auto step = [&](uint32_t p, uint32_t e, uint32_t* n) -> uint32_t {
-        if (p >= lim) return e;
-        const uint32_t p15 = lbits_pad(L, p, 15);
-        uint32_t v = l1[p15 >> (15 - kHufL1)];
-        if (!v) v = a.lut[p15];
-        const uint32_t len = v >> 8;
-        *n += len ? 1u : 0u;
-        return p + (len ? len : 1u);
-    };
-    // slot u of this thread: s = u kTPB + tid, chunk s / 16, entry s % 16 (15: none)
-    auto kc_of = [&](int u) { return (u * kTPB + tid) >> 4; };
-    const int d = tid & 15;
-    uint32_t p[U], n1[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        p[u] = s0 + uint32_t(kc_of(u)) * C + uint32_t(d);
-        n1[u] = 0;
-    }
-    // the sync walks, the thread's U slots interleaved (independent chains: their LDS reads overlap)
-    for (;;) {
-        bool any = false;
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int kc = kc_of(u);
-            const uint32_t cs = s0 + uint32_t(kc) * C, ce = cs + C;
-            if (d < kHufD && kc < m && p[u] < min(cs + kHufSync, ce)) {
-                p[u] = step(p[u], ce, &n1[u]);
-                any = true;
-            }
-        }
-        if (!any) break;
-    }
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const int kc = kc_of(u);
-        const bool act = d < kHufD && kc < m;
-        p[u] = min(p[u], s0 + uint32_t(kc + 1) * C);
-        P[u * kTPB + tid] = act ? p[u] : 0xFFFFFFFFu;
-    }
-    __syncthreads();
-    // the first entry of the chunk standing on the same boundary leads; leaders still inside the
-    // chunk are the survivors
-    int lead[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const int kc = kc_of(u), sl = u * kTPB + tid;
-        const uint32_t ce = s0 + uint32_t(kc + 1) * C;
-        lead[u] = d;
-        if (d < kHufD && kc < m) {
-            for (int j = 0; j < d; j++)
-                if (P[(kc << 4) + j] == p[u]) {
-                    lead[u] = j;
-                    break;
-                }
-            if (lead[u] == d) {
-                if (p[u] < ce) {
-                    R[atomicAdd(&R[S], 1u)] = uint32_t(sl);
-                } else {
-                    X[sl] = p[u];
-                    K2[sl] = 0;
-                    M[sl] = p[u];
-                    KM[sl] = 0;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    const uint32_t nr = R[S];
-    for (uint32_t r = tid; r < nr; r += kTPB) {
-        const uint32_t t = R[r], e = s0 + ((t >> 4) + 1u) * C, mid = e - C / 2u;
-        uint32_t q = P[t], n2 = 0;
-        while (q < mid) q = step(q, e, &n2);  // (the sync walk ends well before the middle)
-        M[t] = q;
-        KM[t] = uint16_t(n2);
-        while (q < e) q = step(q, e, &n2);
-        X[t] = q;
-        K2[t] = uint16_t(n2);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const int kc = kc_of(u);
-        if (d >= kHufD || kc >= m) continue;
-        const uint32_t ce = s0 + uint32_t(kc + 1) * C;
-        const int lt = (kc << 4) + lead[u], k = k0 + kc;
-        tab[size_t(k) * kHufD + d] = uint16_t(X[lt] - ce);
-        cnt[size_t(k) * kHufD + d] = uint16_t(n1[u] + K2[lt]);
-        mo[size_t(k) * kHufD + d] = uint16_t(M[lt] - (ce - C));  // (from the chunk's first bit)
-        mc[size_t(k) * kHufD + d] = uint16_t(n1[u] + KM[lt]);
-    }
-}
-
-// The true entry of every chunk through the composed tables, its symbol count from the table pass,
-// and the workgroup scan of the counts (base[k], wgsum[g]) -- no walk.
-// B (image batch): blockIdx.y = the image; lvl[] stays image 0's -- this image's arrays lie img_tab
-// entries after -- and is indexed by constants only, as in rec_chunk_entry.  A chunk past its
-// image's stream counts nothing (its table rows say so).
-template <bool B = false>
-__global__ __launch_bounds__(kTPB) void huf_count_kernel(HufArgs a, const uint16_t* cnt) {
-    __shared__ alignas(8) uint32_t scratch[8];
-    huf_image<B>(a);
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t c = 0;
-    if (k < a.nchunks) {
-        const uint64_t cstart = a.start_bit + uint64_t(k) * a.chunk_bits;
-        int u = k;
-        for (int l = 0; l < a.levels; l++) u /= kHufG;
-        uint32_t x = a.E[u];
-        if constexpr (B) {
-            const size_t img = size_t(blockIdx.y) * a.img_tab;
-            cnt += img;
-#pragma unroll
-            for (int l = kRecMaxLevels - 1; l >= 0; l--) {
-                if (l < a.levels) {
-                    int ul = k;
-#pragma unroll
-                    for (int m = 0; m < l; m++) ul /= kHufG;
-                    x = a.lvl[l][img + size_t(ul) * kHufD + x];
-                }
-            }
-        } else {
-            for (int l = a.levels - 1; l >= 0; l--) {
-                int ul = k;
-                for (int m = 0; m < l; m++) ul /= kHufG;
-                x = a.lvl[l][size_t(ul) * kHufD + x];
-            }
-        }
-        a.entry[k] = cstart + x;
-        c = cnt[size_t(k) * kHufD + x];
-        a.count[k] = c;
-    }
-    uint32_t tot;
-    const uint32_t ex = block_excl_scan(c, scratch, &tot);
-    if (k < a.nchunks) a.base[k] = ex;
-    if (threadIdx.x == 0) a.wgsum[blockIdx.x] = tot;
-}
-
-// The emitting walk: every chunk again from its entry, over the workgroup's chunks' bits staged
-// in LDS (a step reads LDS, not the stream in memory: the walk is one dependent chain per lane,
-// and the ~800 waves of a 4K payload are too few to hide a memory round trip per code), its
-// symbols into LDS at the chunk's place in the workgroup's output, then the workgroup's output
-// copied out whole (consecutive lanes, consecutive bytes) -- a lane writing its own chunk's bytes
-// straight to memory touches 64 lines per store instruction.  A workgroup whose output exceeds the
-// buffer writes from the walk.  A position no code prefixes flags the stream (changed[1]).
-#ifndef IE_HUF_EMIT_LDS
-#define IE_HUF_EMIT_LDS 40960
-#endif
-constexpr int kHufEmitT = 2 * kTPB;  // emit threads: two per chunk (its halves, split at the
-                                     // middle boundary the table pass recorded)
-// B (image batch): blockIdx.y = the image (huf_image), writing into its own slot of out_cap bytes;
-// a workgroup whose chunks all lie past its image's stream has nothing to write.  (The same LDS
-// as the single-stream form: the batch adds none.)
-template <bool B = false>
-__global__ __launch_bounds__(kHufEmitT) void huf_emit_kernel(HufArgs a, const uint16_t* mo, const uint16_t* mc) {
-    __shared__ uint16_t l1[1 << kHufL1];
-    __shared__ alignas(8) uint64_t scratch[kHufEmitT / 64];
-    __shared__ uint8_t sym[IE_HUF_EMIT_LDS > 0 ? IE_HUF_EMIT_LDS : 1];
-    extern __shared__ uint32_t L[];  // the workgroup's chunks' bits (+ 64 past the last)
-    const int tid = threadIdx.x, j = tid % kTPB, half = tid / kTPB;
-    huf_image<B>(a);
-    if constexpr (B) {
-        const size_t img = size_t(blockIdx.y) * a.img_tab;
-        mo += img;
-        mc += img;
-    }
-    const uint32_t C = uint32_t(a.chunk_bits);
-    const int k0 = blockIdx.x * kTPB, m = min(kTPB, a.nchunks - k0);
-    const uint64_t c0 = a.start_bit + uint64_t(k0) * C;
-    if constexpr (B) {
-        if (c0 >= a.nbits) return;
-    }
-    const uint64_t base = c0 & ~31ull;
-    const uint32_t s0 = uint32_t(c0 - base);
-    stage_words_pad(L, a.words, base >> 5, int((s0 + uint32_t(m) * C + 64) >> 5) + 2, a.nbits, tid, kHufEmitT);
-    huf_l1(a.lut, l1);  // (ends with a barrier: L staged too)
-    // the symbols before this workgroup's chunks: the totals of the workgroups before it
-    uint64_t part = 0;
-    for (int i = tid; i < int(blockIdx.x); i += kHufEmitT) part += a.wgsum[i];
-    const uint64_t ws = wave_sum64(part);
-    if ((tid & 63) == 0) scratch[tid >> 6] = ws;
-    __syncthreads();
-    uint64_t pre = 0;
-#pragma unroll
-    for (int w = 0; w < kHufEmitT / 64; w++) pre += scratch[w];
-    const uint32_t tot = a.wgsum[blockIdx.x];
-    const bool staged = IE_HUF_EMIT_LDS > 0 && tot <= uint32_t(IE_HUF_EMIT_LDS);
-    const int k = k0 + j;
-    if (j < m) {
-        const uint32_t lim = uint32_t(min<uint64_t>(a.nbits - base, uint64_t(s0) + uint64_t(m) * C));
-        const uint32_t cs = s0 + uint32_t(j) * C, e = cs + C;
-        const uint32_t x = uint32_t(a.entry[k] - (a.start_bit + uint64_t(k) * C));  // the true entry offset
-        const uint32_t mid = cs + mo[size_t(k) * kHufD + x];
-        uint32_t p = half ? mid : cs + x, c = 0;
-        const uint32_t end = half ? e : mid;
-        const uint64_t at = a.base[k] + (half ? mc[size_t(k) * kHufD + x] : 0u);
-        uint8_t* o = staged ? sym + at : a.out + pre + at;
-        const uint64_t room = staged ? ~0ull : (a.out_cap > pre + at ? a.out_cap - pre - at : 0ull);
-        while (p < end && p < lim) {
-            const uint32_t p15 = lbits_pad(L, p, 15);
-            uint32_t v = l1[p15 >> (15 - kHufL1)];
-            if (!v) v = a.lut[p15];
-            const uint32_t len = v >> 8;
-            if (!len) {
-                atomicOr(&a.changed[1], 1u);
-                break;
-            }
-            if (c >= room) {
-                atomicOr(&a.changed[0], 1u);
-                break;
-            }
-            o[c++] = uint8_t(v);
-            p += len;
-        }
-    }
-    if (!staged) return;
-    __syncthreads();
-    if (pre + tot > a.out_cap && tid == 0) atomicOr(&a.changed[0], 1u);
-    for (uint32_t i = tid; i < tot && pre + i < a.out_cap; i += kHufEmitT) a.out[pre + i] = sym[i];
-}
-
-// The launches of one decode over a.nchunks chunks (write = false: table pass, composition, counts
-// and total; write = true: the emit), for one stream or (B) for `images` streams side by side.
-template <bool B>
-static int huf_launch(HufArgs a, uint16_t* tab, uint32_t* E, unsigned* ticket, uint64_t* total, bool write, int images,
-                      hipStream_t s) {
-    const int nchunks = a.nchunks;
-    const uint64_t chunk_bits = a.chunk_bits;
-    const dim3 g((nchunks + kTPB - 1) / kTPB, images), blk(kTPB);
-    if (write) {
-        const uint16_t* cnt = tab + compose_rows<kHufD, kHufG>(nchunks) * kHufD;
-        const uint16_t* mo = cnt + size_t(nchunks) * kHufD;
-        hipLaunchKernelGGL(huf_emit_kernel<B>, g, dim3(kHufEmitT), size_t(pad_words(int(((uint64_t(kTPB) * chunk_bits + 95) >> 5) + 3))) * 4, s,
-                           a, mo, mo + size_t(nchunks) * kHufD);
-        return 0;
-    }
-    const size_t lds = size_t(pad_words(int(((uint64_t(kHufTC) * chunk_bits + 95) >> 5) + 3))) * 4;
-    // the symbol counts after the composition's rows (compose_kernel rewrites the exit tables)
-    uint16_t* cnt = tab + compose_rows<kHufD, kHufG>(nchunks) * kHufD;
-    uint16_t* mo = cnt + size_t(nchunks) * kHufD;  // then the middle boundaries and their counts
-    hipLaunchKernelGGL(huf_table_kernel<B>, dim3((nchunks + kHufTC - 1) / kHufTC, images), blk, lds, s, a, tab, cnt, mo,
-                       mo + size_t(nchunks) * kHufD);
-    const int levels = launch_compose<kHufD, kHufG, B>(tab, nchunks, E, ticket, a.lvl, s, images, a.img_tab, a.img_E);
-    if (levels < 0) return -1;
-    a.levels = levels;
-    a.E = E;
-    hipLaunchKernelGGL(huf_count_kernel<B>, g, blk, 0, s, a, cnt);
-    hipLaunchKernelGGL(huf_total_kernel<B>, dim3(1, images), blk, 0, s, a.wgsum, int(g.x), total, a.img_wg);
-    return levels;
-}
-
-int huffman_decode_device(const uint32_t* W, uint64_t nbits, uint64_t start_bit, const uint16_t* lut,
-                          uint64_t chunk_bits, uint64_t* entry, uint16_t* tab, uint32_t* E, unsigned* ticket,
-                          uint32_t* count, uint64_t* base, unsigned* changed, uint64_t* total, uint8_t* out,
-                          bool write, hipStream_t s, uint64_t out_cap) {
-    const uint64_t span = nbits > start_bit ? nbits - start_bit : 0;
-    const int nchunks = int((span + chunk_bits - 1) / chunk_bits);
-    if (nchunks == 0) return 0;
-    HufArgs a{};
-    a.words = W;
-    a.nbits = nbits;
-    a.start_bit = start_bit;
-    a.chunk_bits = chunk_bits;
-    a.nchunks = nchunks;
-    a.lut = lut;
-    a.entry = entry;
-    a.count = count;
-    a.wgsum = count + nchunks;  // [ceil(nchunks / kTPB)] after the counts (huffman_count_words)
-    a.changed = changed;
-    a.base = base;
-    a.out = out;
-    a.out_cap = out_cap;
-    return huf_launch<false>(a, tab, E, ticket, total, write, 1, s);
-}
-
-size_t huffman_batch_tab(int nchunks) {
-    return ((compose_rows<kHufD, kHufG>(nchunks) + 3 * size_t(nchunks)) * kHufD + 7) / 8 * 8;
-}
-uint32_t huffman_batch_wg(int nchunks) { return uint32_t((nchunks + kTPB - 1) / kTPB); }
-uint32_t huffman_batch_entries() { return uint32_t(kHufG); }
-
-int huffman_decode_images(const HufBatch& b, bool write, hipStream_t s) {
-    if (b.nchunks <= 0 || b.images <= 0) return 0;
-    HufArgs a{};
-    a.words = b.words;
-    a.chunk_bits = b.chunk_bits;
-    a.nchunks = b.nchunks;
-    a.lut = b.lut;
-    a.entry = b.entry;
-    a.count = b.count;
-    a.wgsum = b.wgsum;
-    a.changed = b.flags;
-    a.base = b.base;
-    a.out = b.out;
-    a.out_cap = b.out_pitch;
-    a.img_words = b.img_words;
-    a.img_nbits = b.nbits;
-    a.img_start = b.start_bit;
-    a.img_tab = huffman_batch_tab(b.nchunks);
-    a.img_chunks = uint32_t(b.nchunks);
-    a.img_wg = huffman_batch_wg(b.nchunks);
-    a.img_E = uint32_t(kHufG);
-    a.out_pitch = b.out_pitch;
-    return huf_launch<true>(a, b.tab, b.E, nullptr, b.total, write, b.images, s);
-}
-
-size_t huffman_table_rows(uint64_t nbits, uint64_t start_bit, uint64_t chunk_bits) {
-    const uint64_t span = nbits > start_bit ? nbits - start_bit : 0;
-    const int nchunks = int((span + chunk_bits - 1) / chunk_bits);
-    return nchunks ? (compose_rows<kHufD, kHufG>(nchunks) + 3 * size_t(nchunks)) * kHufD : 0;  // (+ counts, middles)
 }
 
 }  // namespace ie

@@ -1,6 +1,6 @@
 // imageencoder_amd/csrc/ie_device.h -- structures shared by the host context (ie_capi.cpp) and
-// the gfx950 kernels (ie_encode.hip, ie_encode4p.hip, ie_huffman.hip, ie_decode.hip, ie_pframe.hip,
-// ie_probe.hip).
+// the gfx950 kernels (ie_encode.hip, ie_encode4p.hip, ie_huffman.hip, ie_decode.hip,
+// ie_huffman_decode.hip, ie_pframe.hip, ie_probe.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -238,7 +238,7 @@ struct RecParseArgs {
     uint16_t* lvl[kRecMaxLevels];  // set by the launcher: the table array of every level
     int levels;
     uint32_t* E;            // [<= G] entry offset of every top-level composite
-    unsigned* ticket;       // [1]: the composition ticket, 0 before the launch (left 0)
+    uint64_t reserved0;     // unused: keeps the later members' offsets (profiles/decode_split_isa.txt)
     uint16_t* pos;          // [nchunks][kRecPosCap] record positions (relative to the chunk's word)
     uint32_t* cnt;          // [nchunks] records of every chunk
     uint32_t* lbase;        // [nchunks] records before every chunk within its count-pass workgroup
@@ -246,7 +246,7 @@ struct RecParseArgs {
     int seg;                // chunks per count-pass wave (rec_count_seg): a workgroup covers 4 * seg
     uint64_t* total;        // records on the true path
     uint64_t* end_out;      // end bit of the last block's record
-    unsigned long long* stats;  // diagnostics (IE_DEC_STATS): walk steps; nullptr = off
+    uint64_t reserved1;     // unused: as reserved0
     unsigned long long* wstamp; // diagnostics (IE_DEC_STAMPS): [table waves][8] phase times; nullptr = off
     int tm;                 // chunks per table wave (rec_table_geometry)
     int hbits;              // log2 of a table wave's claim slots
@@ -279,6 +279,9 @@ struct RecParseArgs {
 void rec_table_geometry(uint32_t C, int n, int* tm, int* hbits);
 int rec_group_chunks(int n);
 int rec_entry_span(int n);
+// Rows of D entries the parse of nchunks chunks needs in RecParseArgs::tab (the chunks' tables and
+// every level's composites), and the composition levels over them (not capped at kRecMaxLevels).
+size_t rec_table_rows(size_t nchunks, int n, int* levels);
 size_t rec_decode_lds(uint32_t C, int n);
 int rec_count_seg(uint32_t C);
 // Returns the number of composition levels (< 0: too many chunks).
@@ -289,15 +292,15 @@ int launch_rec_parse_decode_images(RecParseArgs a, const DecArgs& d, int n, int 
 // the speculative form (a.spec, a.fail set): speculative walks, verifying count pass, decode
 void launch_rec_spec_decode(const RecParseArgs& a, const DecArgs& d, int n, hipStream_t s);
 
-// Huffman decode (ie_decode.hip): write = false runs the exact parse (per-chunk transfer tables
-// over the 15 entry offsets, composed) + the counting walk + scan and leaves the symbol count in
-// *total (device); write = true then emits the symbols into out.  tab: huffman_table_rows()
-// 16-bit words; E: at least 256 words; ticket: 0 (left 0).  Returns the composition levels (< 0
+// Huffman decode (ie_huffman_decode.hip): write = false runs the exact parse (per-chunk transfer
+// tables over the 15 entry offsets, composed) + the counting walk + scan and leaves the symbol
+// count in *total (device); write = true then emits the symbols into out.  tab:
+// huffman_table_rows() 16-bit words; E: at least 256 words.  Returns the composition levels (< 0
 // on error).
 int huffman_decode_device(const uint32_t* W, uint64_t nbits, uint64_t start_bit, const uint16_t* lut,
-                          uint64_t chunk_bits, uint64_t* entry, uint16_t* tab, uint32_t* E, unsigned* ticket,
-                          uint32_t* count, uint64_t* base, unsigned* changed, uint64_t* total, uint8_t* out,
-                          bool write, hipStream_t s, uint64_t out_cap = ~0ull);
+                          uint64_t chunk_bits, uint64_t* entry, uint16_t* tab, uint32_t* E, uint32_t* count,
+                          uint64_t* base, unsigned* changed, uint64_t* total, uint8_t* out, bool write, hipStream_t s,
+                          uint64_t out_cap = ~0ull);
 size_t huffman_table_rows(uint64_t nbits, uint64_t start_bit, uint64_t chunk_bits);
 
 // The same decode for `images` streams side by side in one set of launches (the kernels' batch

@@ -4,8 +4,8 @@ dimension, one chunk plan for the batch -- against the CPU oracle's per-bit walk
 byte for byte including the symbols the padding bits decode to, and against the single-stream
 ie_huffman_decode on the same stream.
 
-The streams are the outputs of codec.huffman_encode.  Chunk constants of ie_decode.hip: 1024-bit
-chunks, kHufTC = 64 chunks per table workgroup, kTPB = 256 chunks per count / emit workgroup,
+The streams are the outputs of codec.huffman_encode.  Chunk constants of ie_huffman_decode.hip:
+1024-bit chunks, kHufTC = 64 chunks per table workgroup, kTPB = 256 chunks per count / emit workgroup,
 kHufG = 256 tables per composition group.
 
 b"\\x07\\x08" gains nothing from the Huffman pass, so its file carries no dictionary (the '0' + the

@@ -9,6 +9,12 @@ template argument).  Per function the instruction stream is compared line by lin
 comments, directive lines, the numbers of compiler labels and symbol names; for kernels the
 .amdhsa_* descriptor and the register / scratch / LDS / kernarg / workgroup-size metadata must be
 equal too.  Prints one line per function; exit status 1 on any difference or unmatched function.
+
+--mask-kernarg, for a change that only removes or adds members of a kernel-argument struct, masks
+exactly two things: the immediate offset of scalar loads whose base is the kernel-argument pointer
+(the user SGPR pair the kernel's descriptor assigns to it; registers and widths still compare), and
+the kernarg-size lines (.amdhsa_kernarg_size in the descriptor, kernarg_segment_size in the
+metadata).
 """
 import argparse
 import difflib
@@ -57,11 +63,27 @@ def parse(path):
     return {n: f for n, f in funcs.items() if f["code"]}  # (data symbols have no instructions)
 
 
+def mask_kernarg(f):
+    """Drop what moves when the kernel-argument struct changes size (kernels only)."""
+    if not f["desc"]:
+        return
+    user = {m.group(1): int(m.group(2)) for m in (re.match(r"\.amdhsa_user_sgpr_(\w+) (\d+)$", d) for d in f["desc"]) if m}
+    # user SGPRs are assigned in this order: the kernarg pointer follows the enabled ones before it
+    lo = 4 * user.get("private_segment_buffer", 0) + 2 * user.get("dispatch_ptr", 0) + 2 * user.get("queue_ptr", 0)
+    load = re.compile(rf"^(s_load_\w+ \S+ s\[{lo}:{lo + 1}\],) (?:0x[0-9a-f]+|\d+)\b")
+    if user.get("kernarg_segment_ptr"):
+        f["code"] = [load.sub(r"\1 KERNARG_OFFSET", c) for c in f["code"]]
+    f["desc"] = [d for d in f["desc"] if not d.startswith(".amdhsa_kernarg_size ")]
+    f["kernarg"] = f["meta"].pop("kernarg_segment_size", None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--old", nargs="+", required=True)
     ap.add_argument("--new", nargs="+", required=True)
     ap.add_argument("--rename", nargs=2, metavar=("REGEX", "REPL"))
+    ap.add_argument("--mask-kernarg", action="store_true",
+                    help="ignore kernel-argument load offsets and the kernarg size (a struct member removed)")
     ap.add_argument("-v", action="store_true", help="print the first differing lines")
     a = ap.parse_args()
     old, new = {}, {}
@@ -70,6 +92,9 @@ def main():
             old[re.sub(a.rename[0], a.rename[1], n) if a.rename else n] = f
     for p in a.new:
         new.update(parse(p))
+    if a.mask_kernarg:
+        for f in list(old.values()) + list(new.values()):
+            mask_kernarg(f)
     rc = 0
     for n in sorted(set(old) | set(new)):
         if n not in old or n not in new:
@@ -79,6 +104,8 @@ def main():
         o, w = old[n], new[n]
         same = o["code"] == w["code"] and o["desc"] == w["desc"] and o["meta"] == w["meta"]
         res = " ".join(f"{k}={v}" for k, v in w["meta"].items() if v is not None)
+        if w.get("kernarg") is not None:  # (masked: shown, not compared)
+            res += f" kernarg_segment_size={o.get('kernarg')}->{w['kernarg']}"
         print(f"{n}: {len(w['code'])} lines {res} {'identical' if same else 'DIFFERENT'}")
         if not same:
             rc = 1
