@@ -12,6 +12,7 @@ There is no CPU fallback: importing succeeds without the library, but constructi
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -89,6 +90,10 @@ def load_library(path: str | None = None) -> C.CDLL:
         L.ie_probe_sizes.restype = C.c_int
         L.ie_probe_sizes.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, u16p, C.c_int,
                                      u64p]
+    if hasattr(L, "ie_probe_rd"):  # (absent from an older IE_LIB build under comparison)
+        L.ie_probe_rd.restype = C.c_int
+        L.ie_probe_rd.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, u16p, C.c_int,
+                                  u64p, u64p]
     for name in ("ie_huffman_hist", "ie_huffman_pack", "ie_bitcopy", "ie_decode_frames"):
         if hasattr(L, name):
             getattr(L, name).restype = C.c_int
@@ -165,6 +170,10 @@ def load_host_library(path: str | None = None) -> C.CDLL:
         H.ieh_encode_image_budget.restype = C.c_int64
         H.ieh_encode_image_budget.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                               C.c_size_t, vp, C.c_size_t, ip]
+    if hasattr(H, "ieh_encode_image_quality"):  # (absent from an older IE_LIB build under comparison)
+        H.ieh_encode_image_quality.restype = C.c_int64
+        H.ieh_encode_image_quality.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.c_uint64, vp, C.c_size_t, ip, C.POINTER(C.c_uint64)]
     H.ieh_encode_video.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, vp, C.c_size_t]
     H.ieh_encode_video_gop.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
@@ -257,6 +266,20 @@ def budget_ladder() -> list[int]:
     H = load_host_library()
     out = (C.c_int * 32)()
     return list(out[: H.ieh_budget_ladder(out)])
+
+
+def sse_for_psnr(psnr: float, npixels: int) -> int:
+    """The largest squared error of ``npixels`` 8-bit pixels whose PSNR is still at least ``psnr``
+    dB: ``floor(npixels * 255**2 / 10**(psnr / 10))``."""
+    return int(math.floor(npixels * 255.0 ** 2 / 10.0 ** (psnr / 10.0)))
+
+
+def psnr_of_sse(sse: int, npixels: int) -> float:
+    """The PSNR in dB of a squared error ``sse`` over ``npixels`` 8-bit pixels:
+    ``10 log10(npixels * 255**2 / sse)``; ``inf`` for 0."""
+    if sse == 0:
+        return math.inf
+    return 10.0 * math.log10(npixels * 255.0 ** 2 / sse)
 
 
 def stream_bound(w: int, h: int, n: int, nframes: int = 1, start_bit: int = 0) -> int:
@@ -510,6 +533,36 @@ class Codec:
                                         nq, bits.ctypes.data_as(u64p)))
         return bits
 
+    def probe_rd(self, y, w: int, h: int, qs, nframes: int = 1, rle: bool = True, stride: int | None = None,
+                 frame_pitch: int | None = None, out=None):
+        """:meth:`probe_sizes`, and the distortion with it (ie_probe_rd): ``(bits, sse)``, each of
+        shape ``(nq, nframes)`` uint64.  ``sse[m, f]`` is the exact sum over frame f's pixels of
+        (decoded - original)^2, the decoded pixel being what :meth:`decode_frames` writes for the
+        stream :meth:`encode_frames` writes after ``set_quant(qs[m])`` with the same ``rle``.  The
+        codec's own matrix is left as it was.  ``out``: an optional pair ``(bits, sse)`` of device
+        tensors of ``nq * nframes`` 64-bit entries each (``bits`` may be None), which receive the
+        sums instead -- the call is then asynchronous and returns ``out``."""
+        stride = w if stride is None else stride
+        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        nn = (self.n or 0) ** 2
+        qs = np.ascontiguousarray(np.asarray(qs, dtype=np.uint16).reshape(-1, nn) if nn else
+                                  np.asarray(qs, dtype=np.uint16))
+        nq = qs.shape[0] if nn else 1
+        u64p = C.POINTER(C.c_uint64)
+        if out is not None:
+            dbits, dsse = out
+            if any(t is not None and _nbytes(t) < 8 * nq * nframes for t in (dbits, dsse)):
+                raise IEError(IE_EINVAL, "probe_rd: out holds fewer than nq * nframes 64-bit entries")
+            self._chk(self.L.ie_probe_rd(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, int(rle), qs.ctypes.data,
+                                         nq, None if dbits is None else C.cast(C.c_void_p(_ptr(dbits)), u64p),
+                                         None if dsse is None else C.cast(C.c_void_p(_ptr(dsse)), u64p)))
+            return out
+        bits = np.zeros((max(nq, 1), nframes), dtype=np.uint64)
+        sse = np.zeros((max(nq, 1), nframes), dtype=np.uint64)
+        self._chk(self.L.ie_probe_rd(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, int(rle), qs.ctypes.data,
+                                     nq, bits.ctypes.data_as(u64p), sse.ctypes.data_as(u64p)))
+        return bits, sse
+
     def host_array(self, nbytes: int) -> np.ndarray:
         """A uint8 numpy array in page-locked host memory (ie_host_alloc): host buffers the
         streamed path DMAs directly.  Freed when the array (and the codec) are gone."""
@@ -640,6 +693,34 @@ class Codec:
             raise e
         self.n = n
         return out[: int(r)].tobytes(), int(pc.value)
+
+    def encode_image_quality(self, y, w: int, h: int, q, n: int, max_sse: int | None = None,
+                             psnr: float | None = None, rle: bool = True, huffman: bool = True,
+                             mode: int = MODE_FAST):
+        """An image file with the coarsest probed scale of ``q`` whose distortion -- the squared
+        error of the decoded pixels, :meth:`probe_rd` -- is at most ``max_sse``
+        (ieh_encode_image_quality): ``(bytes, percent, sse)``.  Exactly one of ``max_sse`` and
+        ``psnr`` (dB, turned into a squared error by :func:`sse_for_psnr`) is given.  Raises
+        ``IEError(IE_ECAP, ...)`` (``e.percent`` = 25) when no scale meets it.  The codec's matrix
+        afterwards is the chosen one."""
+        if (max_sse is None) == (psnr is None):
+            raise IEError(IE_EINVAL, "encode_image_quality: give exactly one of max_sse and psnr")
+        if max_sse is None:
+            max_sse = sse_for_psnr(psnr, w * h)
+        H = load_host_library()
+        q = np.ascontiguousarray(np.asarray(q, dtype=np.uint16).ravel())
+        cap = stream_bound(w, h, n, 1, 2048) + 64
+        out = np.zeros(cap, dtype=np.uint8)
+        pc, se = C.c_int(0), C.c_uint64(0)
+        r = H.ieh_encode_image_quality(self.h, _ptr(y), w, h, q.ctypes.data, n, int(rle), int(huffman), mode,
+                                       min(max(int(max_sse), 0), 2 ** 64 - 1), out.ctypes.data, cap, C.byref(pc),
+                                       C.byref(se))
+        if r < 0:
+            e = IEError(int(r), self.L.ie_last_error(self.h).decode())
+            e.percent = int(pc.value)
+            raise e
+        self.n = n
+        return out[: int(r)].tobytes(), int(pc.value), int(se.value)
 
     def encode_video_file(self, yuv, w: int, h: int, q, n: int, rle: bool = True, huffman: bool = True,
                           merange: int = 0, mode: int = MODE_FAST, gop: int = 1) -> bytes:

@@ -572,16 +572,18 @@ int64_t ieh_encode_image(ie_ctx* c, const uint8_t* y, int w, int h, const uint16
     return int64_t(v.size());
 }
 
-// ---- rate control: scale the matrix until the file fits a byte budget (ie_probe_sizes)
+// ---- rate control: scale the matrix until the file fits a byte budget (ie_probe_sizes) or until
+// its distortion meets a target (ie_probe_rd)
 namespace {
 // round(100 * 2^(j/4)), j = -8 .. 23: the scales the budget search probes first
 const int kBudgetLadder[32] = {25,  30,  35,  42,  50,  59,  71,   84,   100,  119,  141,  168,  200,  238,  283,  336,
                                400, 476, 566, 673, 800, 951, 1131, 1345, 1600, 1903, 2263, 2691, 3200, 3805, 4525, 5382};
 
-// File bytes (before any Huffman pass) of every percent in `pc` for one frame: one ie_probe_sizes
-// call over the distinct scaled matrices.
-int budget_sizes(ie_ctx* c, const uint8_t* y, dc::FileParams p, const uint16_t* base, const std::vector<int>& pc,
-                 std::vector<uint64_t>& bytes) {
+// File bytes (before any Huffman pass) of every percent in `pc` for one frame, and with `sse` the
+// squared error of the decoded frame: one ie_probe_sizes / ie_probe_rd call over the distinct
+// scaled matrices, mapped back to the percents.
+int probe_percents(ie_ctx* c, const uint8_t* y, dc::FileParams p, const uint16_t* base, const std::vector<int>& pc,
+                   std::vector<uint64_t>& bytes, std::vector<uint64_t>* sse = nullptr) {
     const int nn = p.n * p.n;
     std::vector<uint16_t> qs;        // the distinct matrices, in order of first use
     std::vector<int> which(pc.size());
@@ -595,17 +597,70 @@ int budget_sizes(ie_ctx* c, const uint8_t* y, dc::FileParams p, const uint16_t* 
         which[i] = int(m);
     }
     const int nq = int(qs.size() / size_t(nn));
-    std::vector<uint64_t> bits(static_cast<size_t>(nq), 0);
-    const int r = ie_probe_sizes(c, y, p.w, p.h, size_t(p.w), 0, 1, p.rle ? 1 : 0, qs.data(), nq, bits.data());
+    std::vector<uint64_t> bits(static_cast<size_t>(nq), 0), se(static_cast<size_t>(nq), 0);
+    const int r = sse ? ie_probe_rd(c, y, p.w, p.h, size_t(p.w), 0, 1, p.rle ? 1 : 0, qs.data(), nq, bits.data(), se.data())
+                      : ie_probe_sizes(c, y, p.w, p.h, size_t(p.w), 0, 1, p.rle ? 1 : 0, qs.data(), nq, bits.data());
     if (r) return r;
     bytes.resize(pc.size());
+    if (sse) sse->resize(pc.size());
     for (size_t i = 0; i < pc.size(); i++) {
         p.q = qs.data() + size_t(which[i]) * nn;
         util::BitStreamWriter hdr(64);
         dc::write_header(hdr, p);  // (its length depends on the matrix's widest value)
         bytes[i] = (uint64_t(hdr.get_position()) + bits[size_t(which[i])] + 7) / 8;
+        if (sse) (*sse)[i] = se[size_t(which[i])];
     }
     return IE_OK;
+}
+
+// The integers p0 + ceil(i (p1 - p0) / 33), i = 1 .. 32, strictly between two ladder entries: at
+// most 32 of them, ascending.
+std::vector<int> refine_percents(int p0, int p1) {
+    std::vector<int> fine;
+    for (int i = 1; i <= 32; i++) {
+        const int v = p0 + (i * (p1 - p0) + 32) / 33;
+        if (v > p0 && v < p1 && (fine.empty() || fine.back() != v)) fine.push_back(v);
+    }
+    return fine;
+}
+
+// A host frame goes to the device once, for the probes and the encode.
+int frame_on_device(ie_ctx* c, const uint8_t* y, int w, int h, const uint8_t** dy) {
+    *dy = y;
+    if (!dc::is_device(c, y) && w > 0 && h > 0) {
+        dc::Scratch& s = dc::scratch(c);
+        const size_t px = size_t(w) * size_t(h);
+        int r;
+        if ((r = s.pix.reserve(px))) return r;
+        if ((r = ie_memcpy(c, s.pix.p, y, px))) return r;
+        *dy = s.pix.p;
+    }
+    return IE_OK;
+}
+
+// The file under `base` scaled to `percent`, which the probe sized at probed_bytes before the Huffman pass.
+int64_t encode_scaled(ie_ctx* c, const uint8_t* dy, dc::FileParams p, const uint16_t* base, int percent,
+                      uint64_t probed_bytes, const char* what, uint8_t* out, size_t cap, int* chosen) {
+    std::vector<uint16_t> q(static_cast<size_t>(p.n * p.n));
+    ieh_scale_matrix(base, p.n, percent, q.data());
+    p.q = q.data();
+    std::vector<uint8_t> v;
+    std::string err;
+    size_t pre = 0;
+    int r;
+    if ((r = dc::encode_file(c, dy, p, v, err, &pre))) return r;
+    *chosen = percent;
+    if (uint64_t(pre) != probed_bytes) {
+        ie_set_error(c, (std::string(what) + " encode: the file is " + std::to_string(pre) +
+                         " bytes before the Huffman pass, the probe said " + std::to_string(probed_bytes)).c_str());
+        return IE_EDEVICE;
+    }
+    if (v.size() > cap) {
+        ie_set_error(c, "output capacity below the encoded file");
+        return IE_ECAP;
+    }
+    std::memcpy(out, v.data(), v.size());
+    return int64_t(v.size());
 }
 }  // namespace
 
@@ -635,18 +690,11 @@ int64_t ieh_encode_image_budget(ie_ctx* c, const uint8_t* y, int w, int h, const
     p.rle = rle != 0;
     p.huffman = huffman != 0;
     p.mode = mode;
-    // a host frame goes to the device once, for both probes and the encode
-    const uint8_t* dy = y;
-    if (!dc::is_device(c, y) && w > 0 && h > 0) {
-        dc::Scratch& s = dc::scratch(c);
-        const size_t px = size_t(w) * size_t(h);
-        if ((r = s.pix.reserve(px))) return r;
-        if ((r = ie_memcpy(c, s.pix.p, y, px))) return r;
-        dy = s.pix.p;
-    }
+    const uint8_t* dy;
+    if ((r = frame_on_device(c, y, w, h, &dy))) return r;
     std::vector<int> ladder(kBudgetLadder, kBudgetLadder + 32);
     std::vector<uint64_t> size;
-    if ((r = budget_sizes(c, dy, p, base, ladder, size))) return r;
+    if ((r = probe_percents(c, dy, p, base, ladder, size))) return r;
     int i1 = -1;  // the smallest ladder percent whose file fits
     for (int i = 0; i < 32 && i1 < 0; i++)
         if (size[size_t(i)] <= budget_bytes) i1 = i;
@@ -658,15 +706,10 @@ int64_t ieh_encode_image_budget(ie_ctx* c, const uint8_t* y, int w, int h, const
     int best = kBudgetLadder[i1];
     uint64_t best_bytes = size[size_t(i1)];
     if (i1 > 0) {  // the integers between the two ladder entries, at most 32 of them
-        const int p0 = kBudgetLadder[i1 - 1], p1 = kBudgetLadder[i1];
-        std::vector<int> fine;
-        for (int i = 1; i <= 32; i++) {
-            const int v = p0 + (i * (p1 - p0) + 32) / 33;  // p0 + ceil(i (p1 - p0) / 33)
-            if (v > p0 && v < p1 && (fine.empty() || fine.back() != v)) fine.push_back(v);
-        }
+        const std::vector<int> fine = refine_percents(kBudgetLadder[i1 - 1], kBudgetLadder[i1]);
         if (!fine.empty()) {
             std::vector<uint64_t> fsize;
-            if ((r = budget_sizes(c, dy, p, base, fine, fsize))) return r;
+            if ((r = probe_percents(c, dy, p, base, fine, fsize))) return r;
             for (size_t i = 0; i < fine.size(); i++)
                 if (fsize[i] <= budget_bytes) {
                     best = fine[i];
@@ -675,25 +718,52 @@ int64_t ieh_encode_image_budget(ie_ctx* c, const uint8_t* y, int w, int h, const
                 }
         }
     }
-    std::vector<uint16_t> q(static_cast<size_t>(n * n));
-    ieh_scale_matrix(base, n, best, q.data());
-    p.q = q.data();
-    std::vector<uint8_t> v;
-    std::string err;
-    size_t pre = 0;
-    if ((r = dc::encode_file(c, dy, p, v, err, &pre))) return r;
-    *percent = best;
-    if (uint64_t(pre) != best_bytes) {
-        ie_set_error(c, ("budget encode: the file is " + std::to_string(pre) + " bytes before the Huffman pass, the probe said " +
-                         std::to_string(best_bytes)).c_str());
-        return IE_EDEVICE;
-    }
-    if (v.size() > cap) {
-        ie_set_error(c, "output capacity below the encoded file");
+    return encode_scaled(c, dy, p, base, best, best_bytes, "budget", out, cap, percent);
+}
+
+int64_t ieh_encode_image_quality(ie_ctx* c, const uint8_t* y, int w, int h, const uint16_t* base, int n, int rle,
+                                 int huffman, int mode, uint64_t max_sse, uint8_t* out, size_t cap, int* percent,
+                                 uint64_t* sse) {
+    if (!c || !y || !base || !out || !percent || !sse || (n != 4 && n != 8)) return IE_EINVAL;
+    int r;
+    if ((r = ie_set_quant(c, base, n))) return r;  // the probe's block size and transform tables
+    dc::FileParams p;
+    p.w = w;
+    p.h = h;
+    p.n = n;
+    p.rle = rle != 0;
+    p.huffman = huffman != 0;
+    p.mode = mode;
+    const uint8_t* dy;
+    if ((r = frame_on_device(c, y, w, h, &dy))) return r;
+    std::vector<int> ladder(kBudgetLadder, kBudgetLadder + 32);
+    std::vector<uint64_t> size, se;
+    if ((r = probe_percents(c, dy, p, base, ladder, size, &se))) return r;
+    int i0 = -1;  // the largest ladder percent whose distortion meets the target
+    for (int i = 0; i < 32; i++)
+        if (se[size_t(i)] <= max_sse) i0 = i;
+    if (i0 < 0) {
+        *percent = kBudgetLadder[0];
+        ie_set_error(c, "no scale down to 25 % meets the quality");
         return IE_ECAP;
     }
-    std::memcpy(out, v.data(), v.size());
-    return int64_t(v.size());
+    int best = kBudgetLadder[i0];
+    uint64_t best_bytes = size[size_t(i0)], best_se = se[size_t(i0)];
+    if (i0 < 31) {  // the integers between it and the entry above, at most 32 of them
+        const std::vector<int> fine = refine_percents(kBudgetLadder[i0], kBudgetLadder[i0 + 1]);
+        if (!fine.empty()) {
+            std::vector<uint64_t> fsize, fse;
+            if ((r = probe_percents(c, dy, p, base, fine, fsize, &fse))) return r;
+            for (size_t i = 0; i < fine.size(); i++)  // (ascending: the last that meets it is the largest)
+                if (fse[i] <= max_sse) {
+                    best = fine[i];
+                    best_bytes = fsize[i];
+                    best_se = fse[i];
+                }
+        }
+    }
+    *sse = best_se;
+    return encode_scaled(c, dy, p, base, best, best_bytes, "quality", out, cap, percent);
 }
 
 int64_t ieh_encode_video(ie_ctx* c, const uint8_t* yuv, size_t len, int w, int h, const uint16_t* q, int n, int rle,

@@ -233,13 +233,15 @@ struct ie_ctx {
     // every group's reconstructed frames, coefficients, record lengths, tile sums; the wave's
     // position table and the groups' first bits).  The frames' positions in the stream: d_gop_pos.
     iec::Buf<uint8_t> d_gopg;
-    // ie_probe_sizes: the candidate matrices (zig-zag order; pinned, then device: IE_PROBE_MAX of
-    // them), the event after the copy out of the pinned block, the sums when `bits` is host memory
+    // ie_probe_sizes / ie_probe_rd: the candidate matrices (zig-zag order; pinned, then device:
+    // IE_PROBE_MAX of them), the event after the copy out of the pinned block, the sums when the
+    // results are host memory (ie_probe_rd: bits, then sse, read back together into h_probe_out)
     iec::Buf<uint16_t, iec::Mem::Pinned> h_probe_q;
     iec::Buf<uint16_t> d_probe_q;
     iec::Event ev_probe;
     bool probe_recorded = false;
     iec::Buf<uint64_t> d_probe_bits;
+    iec::Buf<uint64_t, iec::Mem::Pinned> h_probe_out;
 };
 
 namespace iec {

@@ -126,7 +126,8 @@ int encode_small_tiles();             // a launch of fewer tiles does not fill t
 void launch_word_scatter(const uint32_t* src, uint32_t* dst, uint64_t pitch_words, int n, hipStream_t s);
 int encode_threads_per_tile();       // threads per encoder workgroup (= tile)
 
-// ie_probe_sizes (ie_probe.hip): the payload bits of every frame under nq candidate matrices.
+// ie_probe_sizes / ie_probe_rd (ie_probe.hip): the payload bits, and the squared error of the
+// decoded pixels, of every frame under nq candidate matrices.
 struct ProbeArgs {
     const uint8_t* y;
     uint64_t stride, frame_pitch;
@@ -135,10 +136,13 @@ struct ProbeArgs {
     int vec_ok;              // rows may be read with 4-byte loads
     int nq;                  // 1 .. IE_PROBE_MAX
     const uint16_t* q;       // [nq][N*N] candidates in ZIG-ZAG order (device)
-    const EncTables* tab;    // P and S of the block size (they do not depend on the matrix)
+    const EncTables* tab;    // P, S and R of the block size (they do not depend on the matrix)
     unsigned long long* bits;  // [nq][nframes], zero before the launch: bits[m * nframes + f] is added to
 };
 void launch_probe_sizes(const ProbeArgs& a, int n, hipStream_t s);
+// the distortion too: sse has the shape and rule of bits, which may then be nullptr
+void launch_probe_rd(const ProbeArgs& a, unsigned long long* sse, int n, hipStream_t s);
+int probe_rd_max_workgroups(int n);  // the grid of launch_probe_rd is min(tiles, this)
 
 struct PackArgs {            // Huffman re-encode / bit copy: one variable-length code per byte
     const uint8_t* in;

@@ -18,6 +18,11 @@
 // over the wave, and lane m keeps candidate m's running sum.  A wave adds its sums to
 // bits[m * nframes + f] with one 64-bit atomic per candidate when its frame changes or its work
 // ends; the sums are integers, so the order does not matter.
+//
+// ie_probe_rd (probe_kernel<N, true>) adds the distortion of every candidate to the same pass: once a
+// candidate's rounded values are in registers, everything the decoder would see is known, so the
+// lanes dequantise, run the inverse transform in the reference's order, clamp and compare with
+// the staged pixel.  See the comment at probe_rd_sse.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -67,25 +72,110 @@ __device__ __forceinline__ uint32_t probe_wave_sum(uint32_t v) {
 }
 
 // Dynamic LDS: [NN][NN] doubles (P transposed; for 4x4 the four blocks' lanes read the same 16
-// columns), then the tile's pixel words [NN/4][TB], then the candidates [nq][NN] uint16 (zig-zag order).
+// columns), with the distortion the inverse rows R [uv][ij] as EncTables holds them, then the
+// tile's pixel words [NN/4][TB], then the candidates [nq][NN] uint16 (zig-zag order).
 template <int N> struct ProbeGeo {
     static constexpr int NN = N * N;
     static constexpr int BPW = 64 / NN;                              // blocks per wave and step
     static constexpr int TB = kProbeWaves * kProbeSteps * BPW;       // blocks per tile
     static constexpr int P_DOUBLES = NN * NN;
     static constexpr int PIX_WORDS = (NN / 4) * TB;
-    static constexpr size_t lds_bytes(int nq) {
-        return size_t(P_DOUBLES) * 8 + size_t(PIX_WORDS) * 4 + ((size_t(nq) * NN * 2 + 7) & ~size_t(7));
+    static constexpr size_t lds_bytes(int nq, bool rd = false) {
+        return size_t(P_DOUBLES) * 8 * (rd ? 2 : 1) + size_t(PIX_WORDS) * 4 + ((size_t(nq) * NN * 2 + 7) & ~size_t(7));
     }
 };
 
+// zig-zag rank of every natural index (the inverse of kProbeZz4 / kProbeZz8)
+struct ProbeIzz4 {
+    int r[16];
+    constexpr ProbeIzz4() : r() {
+        constexpr int zz[16] = {0, 1, 4, 8, 5, 2, 3, 6, 9, 12, 13, 10, 7, 11, 14, 15};
+        for (int z = 0; z < 16; z++) r[zz[z]] = z;
+    }
+};
+__constant__ uint8_t kProbeIzz8[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42,
+                                       3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,
+                                       10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60,
+                                       21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+
+// 4x4, terms UV .. 15 of a pixel's inverse transform: Y[uv] of the lane's own block comes from the
+// row's lane izz(uv) by a DPP row broadcast, R[uv][ij] from LDS (consecutive lanes, consecutive doubles)
+template <int UV>
+__device__ __forceinline__ void probe_idct4_terms(uint32_t any, int ylo, int yhi, const double* Rl, double& t) {
+    if constexpr (UV < 16) {
+        constexpr ProbeIzz4 izz;
+        constexpr int z = izz.r[UV];
+        if ((any >> z) & 1u) {  // (wave-uniform)
+            const int lo = __builtin_amdgcn_update_dpp(0, ylo, 0x150 + z, 0xf, 0xf, false);  // row_newbcast:z
+            const int hi = __builtin_amdgcn_update_dpp(0, yhi, 0x150 + z, 0xf, 0xf, false);
+            t = t + Rl[UV * 16] * __hiloint2double(hi, lo);
+        }
+        probe_idct4_terms<UV + 1>(any, ylo, yhi, Rl, t);
+    }
+}
+
+// The squared error of the lane's pixel under one candidate.  vd: the lane's quantised value as the
+// decoder reads it (lane = zig-zag position kz of its block), qd: the candidate's entry there,
+// Rl: the R column of the lane's pixel (pixel ij = the lane's position within its block, natural
+// order), px: that pixel's byte.
+//
+// Block::processIDCTMulQ (Block.cpp:162-175, algo.cpp:348-358): Y = double(v) * q, then temp[ij] =
+// temp[ij] + R[uv][ij] * Y[uv] over uv ascending in natural order, un-contracted; x = temp + 128.0,
+// clamped to [0, 255] and truncated (Block.cpp:100-107).  The order over uv is kept; what each lane
+// sums is its own pixel.  A zero Y term adds +-0: it leaves every partial sum unchanged but possibly
+// the sign of a zero, which + 128 and the clamp erase (the argument of decode_record,
+// ie_decode.hip), so a term that is zero in every lane of the wave is skipped -- and, for the same
+// reason, a term that is zero may be added where skipping it would cost a branch.  At coarse
+// scales most terms are skipped; at fine scales the 2 N^2 FP64 operations per pixel are the cost.
+//  - 8x8: the wave is one block.  Y moves to natural order through the LDS crossbar (ds_bpermute),
+//    one __ballot gives the non-zero terms as a scalar mask, and a scalar loop walks its bits in
+//    ascending order, four per trip (the R reads of a trip are issued together; a trip's missing
+//    terms are Y = 0 at uv = 0).  Y[uv] is a readlane: the multiply takes it from SGPRs.
+//  - 4x4: four blocks, one per DPP row; a term is skipped when it is zero in all four.
 template <int N>
-__global__ __launch_bounds__(kTPB) void probe_sizes_kernel(ProbeArgs a) {
+__device__ __forceinline__ uint32_t probe_rd_sse(int vd, double qd, const double* Rl, uint32_t px, int lane) {
+    constexpr int NN = N * N;
+    const double Y = double(vd) * qd;
+    int ylo = __double2loint(Y), yhi = __double2hiint(Y);
+    double t = 0.0;
+    if constexpr (N == 8) {
+        const int src = int(kProbeIzz8[lane]) * 4;
+        ylo = __builtin_amdgcn_ds_bpermute(src, ylo);
+        yhi = __builtin_amdgcn_ds_bpermute(src, yhi);
+        uint64_t todo = __ballot(yhi != 0);  // |Y| >= 1 or Y == +0: the high word tells
+        while (todo) {
+            double r[4], y[4];
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int uv = todo ? __builtin_ctzll(todo) : 0;
+                const int lo = __builtin_amdgcn_readlane(ylo, uv), hi = __builtin_amdgcn_readlane(yhi, uv);
+                y[e] = todo ? __hiloint2double(hi, lo) : 0.0;
+                r[e] = Rl[uv * NN];
+                todo &= todo - 1;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; e++) t = t + r[e] * y[e];
+        }
+    } else {
+        const uint64_t nz = __ballot(vd != 0);
+        const uint32_t any = uint32_t(nz | (nz >> 16) | (nz >> 32) | (nz >> 48)) & 0xFFFFu;
+        probe_idct4_terms<0>(any, ylo, yhi, Rl, t);
+    }
+    double x = t + 128.0;
+    x = x < 0.0 ? 0.0 : (x > 255.0 ? 255.0 : x);
+    const int err = int(uint8_t(x)) - int(px);  // in [-255, 255]
+    return uint32_t(err * err);
+}
+
+// RD = false: the sizes alone (ie_probe_sizes); RD = true: the distortion too (ie_probe_rd)
+template <int N, bool RD>
+__global__ __launch_bounds__(kTPB) void probe_kernel(ProbeArgs a, unsigned long long* sse) {
     using G = ProbeGeo<N>;
     constexpr int NN = G::NN, BPW = G::BPW, TB = G::TB;
     extern __shared__ __attribute__((aligned(16))) unsigned char probe_lds[];
     double* Pt = reinterpret_cast<double*>(probe_lds);                        // [ij][kz]
-    uint32_t* pixw = reinterpret_cast<uint32_t*>(Pt + G::P_DOUBLES);          // [word][block of the tile]
+    double* Rn = Pt + G::P_DOUBLES;                                           // RD: [uv][ij]
+    uint32_t* pixw = reinterpret_cast<uint32_t*>(Pt + G::P_DOUBLES * (RD ? 2 : 1));  // [word][block of the tile]
     uint16_t* qz = reinterpret_cast<uint16_t*>(pixw + G::PIX_WORDS);          // [m][kz]
 
     const int tid = int(threadIdx.x), lane = tid & 63, wave = tid >> 6;
@@ -97,12 +187,17 @@ __global__ __launch_bounds__(kTPB) void probe_sizes_kernel(ProbeArgs a) {
         Pt[e] = a.tab->P[probe_zz<N>(z) * NN + ij];
     }
     for (int e = tid; e < a.nq * NN; e += kTPB) qz[e] = a.q[e];
+    if constexpr (RD)
+        for (int e = tid; e < NN * NN; e += kTPB) Rn[e] = a.tab->R[e];
     const double S = a.tab->S[k];
 
     const int nblk = a.bx * a.by;
     const uint64_t tpf = uint64_t((nblk + TB - 1) / TB);
     const uint64_t total = tpf * uint64_t(a.nframes);
     uint32_t mine = 0;  // lane m: candidate m's bits of frame cur_f so far (this wave)
+    // RD, lane m: candidate m's squared error of frame cur_f so far.  A step adds at most 64 * 255^2,
+    // a wave's steps of one frame are not bounded by 2^32: 64 bits.
+    uint64_t mine_se = 0;
     int64_t cur_f = -1;
     const bool owner = kz == NN - 1;  // the block's last lane holds its DPP results
 
@@ -110,9 +205,14 @@ __global__ __launch_bounds__(kTPB) void probe_sizes_kernel(ProbeArgs a) {
         const int64_t f = int64_t(it / tpf);
         const int b0 = int(it % tpf) * TB;
         if (f != cur_f) {
-            if (cur_f >= 0 && lane < a.nq)
-                atomicAdd(&a.bits[uint64_t(lane) * uint64_t(a.nframes) + uint64_t(cur_f)], (unsigned long long)mine);
+            if (cur_f >= 0 && lane < a.nq) {
+                if (!RD || a.bits)
+                    atomicAdd(&a.bits[uint64_t(lane) * uint64_t(a.nframes) + uint64_t(cur_f)], (unsigned long long)mine);
+                if constexpr (RD)
+                    atomicAdd(&sse[uint64_t(lane) * uint64_t(a.nframes) + uint64_t(cur_f)], (unsigned long long)mine_se);
+            }
             mine = 0;
+            mine_se = 0;
             cur_f = f;
         }
         __syncthreads();  // the previous tile's pixels have been read (first pass: the tables are written)
@@ -158,9 +258,12 @@ __global__ __launch_bounds__(kTPB) void probe_sizes_kernel(ProbeArgs a) {
                 }
             }
             const double D = acc * S;
+            uint32_t px = 0;  // RD: the byte of the lane's pixel (pixel kz of block j), before the level shift
+            if constexpr (RD) px = (pixw[(kz >> 2) * TB + j] >> (8 * (kz & 3))) & 0xFFu;
 #pragma unroll 1
             for (int m = 0; m < a.nq; m++) {
-                const double t = D / double(qz[m * NN + kz]);  // IEEE division (Block.cpp:149-152)
+                const double qd = double(qz[m * NN + kz]);
+                const double t = D / qd;  // IEEE division (Block.cpp:149-152)
                 double r = trunc(t);
                 if (fabs(t - r) >= 0.5) r += copysign(1.0, t);  // std::round: half away from zero
                 const int v = int(r);
@@ -189,11 +292,23 @@ __global__ __launch_bounds__(kTPB) void probe_sizes_kernel(ProbeArgs a) {
                 const uint32_t len = a.rle ? 4u + bl * (lw + 1u) : 4u + bl * uint32_t(NN);
                 const uint32_t sum = probe_wave_sum((owner && valid) ? len : 0u);
                 if (lane == m) mine += sum;
+                if constexpr (RD) {
+                    // what the decoder reads: v, but the last value of a record RLE cut short (L == NN, value
+                    // NN - 2 zero: lw above; Block.cpp:388-390) is 0
+                    const int vd = (a.rle && L == uint32_t(NN) && lw != L && owner) ? 0 : v;
+                    const uint32_t se = probe_rd_sse<N>(vd, qd, Rn + kz, px, lane);
+                    const uint32_t ssum = probe_wave_sum(valid ? se : 0u);  // <= 64 * 255^2
+                    if (lane == m) mine_se += ssum;
+                }
             }
         }
     }
-    if (cur_f >= 0 && lane < a.nq)
-        atomicAdd(&a.bits[uint64_t(lane) * uint64_t(a.nframes) + uint64_t(cur_f)], (unsigned long long)mine);
+    if (cur_f >= 0 && lane < a.nq) {
+        if (!RD || a.bits)
+            atomicAdd(&a.bits[uint64_t(lane) * uint64_t(a.nframes) + uint64_t(cur_f)], (unsigned long long)mine);
+        if constexpr (RD)
+            atomicAdd(&sse[uint64_t(lane) * uint64_t(a.nframes) + uint64_t(cur_f)], (unsigned long long)mine_se);
+    }
 }
 
 }  // namespace
@@ -203,9 +318,29 @@ void launch_probe_sizes(const ProbeArgs& a, int n, hipStream_t s) {
     const uint64_t total = uint64_t((a.bx * a.by + tb - 1) / tb) * uint64_t(a.nframes);
     const unsigned grid = unsigned(total < 1024 ? total : 1024);  // persistent workgroups: the tables are staged once each
     if (n == 4)
-        hipLaunchKernelGGL(probe_sizes_kernel<4>, dim3(grid), dim3(kTPB), ProbeGeo<4>::lds_bytes(a.nq), s, a);
+        hipLaunchKernelGGL((probe_kernel<4, false>), dim3(grid), dim3(kTPB), ProbeGeo<4>::lds_bytes(a.nq), s, a, nullptr);
     else
-        hipLaunchKernelGGL(probe_sizes_kernel<8>, dim3(grid), dim3(kTPB), ProbeGeo<8>::lds_bytes(a.nq), s, a);
+        hipLaunchKernelGGL((probe_kernel<8, false>), dim3(grid), dim3(kTPB), ProbeGeo<8>::lds_bytes(a.nq), s, a, nullptr);
+}
+
+int probe_rd_max_workgroups(int n) { return n == 4 ? 1024 : 512; }
+
+void launch_probe_rd(const ProbeArgs& a, unsigned long long* sse, int n, hipStream_t s) {
+    const int tb = n == 4 ? ProbeGeo<4>::TB : ProbeGeo<8>::TB;
+    const uint64_t total = uint64_t((a.bx * a.by + tb - 1) / tb) * uint64_t(a.nframes);
+    // persistent workgroups, as above; 8x8 holds P and R in LDS (64 KiB + pixels + candidates: two
+    // workgroups per CU), so 512 of them are all resident at once
+    const uint64_t cap = uint64_t(probe_rd_max_workgroups(n));
+    const unsigned grid = unsigned(total < cap ? total : cap);
+    if (n == 4) {
+        hipLaunchKernelGGL((probe_kernel<4, true>), dim3(grid), dim3(kTPB), ProbeGeo<4>::lds_bytes(a.nq, true), s, a, sse);
+    } else {
+        // more than the 64 KiB a launch may ask for by default (a refusal shows as the launch's error)
+        const size_t lds = ProbeGeo<8>::lds_bytes(a.nq, true);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&probe_kernel<8, true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+        hipLaunchKernelGGL((probe_kernel<8, true>), dim3(grid), dim3(kTPB), lds, s, a, sse);
+    }
 }
 
 }  // namespace ie

@@ -193,6 +193,27 @@ enum { IE_PROBE_MAX = 64 };
 int ie_probe_sizes(ie_ctx* ctx, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch,
                    int nframes, int use_rle, const uint16_t* q, int nq, uint64_t* bits);
 
+/* ---- Distortion probe: ie_probe_sizes' pass, and with it the squared error of the decoded pixels
+ * of every frame under every candidate ("how good will it look?"), without writing or parsing a bit.
+ *   y .. nq      as ie_probe_sizes: the same arguments, checks, error codes and their order
+ *   sse          required: nq * nframes entries, host or device (8-byte aligned) memory
+ *   bits         optional (NULL: not wanted): the same shape and memory rules; receives exactly what
+ *                ie_probe_sizes writes.  bits and sse are both host or both device memory: a mix is
+ *                IE_EINVAL.
+ * sse[m*nframes + f] = the sum over the pixels of frame f of (d - y)^2, d the pixel that
+ * ie_decode_frames writes for the stream that ie_encode_frames writes after ie_set_quant(ctx,
+ * q + m*n*n, n), with the same use_rle, in either mode.  It is an integer and exact: per block the
+ * kernel restates the quantised values (as the sizes probe), the one lossy rule of the stream (with
+ * use_rle a record of length N*N whose zig-zag value N*N-2 is zero loses its last value,
+ * Block.cpp:388-390), Y = double(v) * q, temp[ij] = temp[ij] + R[uv][ij] * Y[uv] over uv ascending
+ * (algo.cpp:348-358, un-contracted), and x = temp + 128.0 clamped to [0, 255] and truncated
+ * (Block.cpp:100-107).
+ *  - The context's matrix, tables, chain state and ie_last_end_bits are left as they were.
+ *  - With device results the call is asynchronous on the context's stream (the results are zeroed
+ *    there).  With host results it synchronises once and reads both arrays back in one copy. */
+int ie_probe_rd(ie_ctx* ctx, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch,
+                int nframes, int use_rle, const uint16_t* q, int nq, uint64_t* bits, uint64_t* sse);
+
 /* ---- Device memory on the context's stream (for hosts that keep streams device-resident
  * between stages, e.g. the host library's encode -> Huffman pipeline).  ie_memcpy infers the
  * direction of each pointer and is asynchronous only when both are device memory. */

@@ -357,6 +357,22 @@ int ieh_budget_ladder(int* out);
 //  - IE_EDEVICE if the encoded file's size before the Huffman pass ever differs from the probed one.
 int64_t ieh_encode_image_budget(ie_ctx* ctx, const uint8_t* y, int w, int h, const uint16_t* base, int n, int rle,
                                 int huffman, int mode, size_t budget_bytes, uint8_t* out, size_t cap, int* percent);
+// Whole image file (as ieh_encode_image writes it) with the COARSEST probed scale of `base` whose
+// distortion -- the squared error of the decoded pixels against y, ie_probe_rd -- is at most
+// max_sse.  Returns the bytes written, *percent = the scale chosen, *sse = its distortion.
+//  - Distortion is no more monotone in the scale than size is, so the search mirrors the budget
+//    search: ONE ie_probe_rd call over the ladder (distinct matrices only); p0 = the largest ladder
+//    percent with sse <= max_sse, p1 the entry above it; ONE more call over the integers
+//    p0 + ceil(i (p1 - p0) / 33), i = 1 .. 32, strictly between the two; the result is the largest
+//    percent of both sets that meets max_sse.  p0 = 5382 ends the search at once.
+//  - Nothing meets it: IE_ECAP, *percent = 25, nothing written, ie_last_error "no scale down to
+//    25 % meets the quality" (the context's matrix is then `base`).  Otherwise the context's matrix
+//    is the chosen one.  IE_ECAP with another message: cap is below the file.
+//  - IE_EDEVICE if the encoded file's size before the Huffman pass differs from the probed one (the
+//    sizes come along in the same probe calls).
+int64_t ieh_encode_image_quality(ie_ctx* ctx, const uint8_t* y, int w, int h, const uint16_t* base, int n,
+                                 int rle, int huffman, int mode, uint64_t max_sse, uint8_t* out, size_t cap,
+                                 int* percent, uint64_t* sse);
 // gop=1 video file from a YUV420 buffer (frame_count = len / (1.5 w h)).
 int64_t ieh_encode_video(ie_ctx* ctx, const uint8_t* yuv, size_t len, int w, int h, const uint16_t* q, int n,
                          int rle, int huffman, int merange, int mode, uint8_t* out, size_t cap);
