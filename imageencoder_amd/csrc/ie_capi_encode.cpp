@@ -12,8 +12,13 @@ int launch_chain(ie_ctx* c, const Launch& L) {
     const Geometry g = geometry(L.w, L.h, c->n, L.nframes);
     // a launch too small to fill the chip: its tiles reach the look-back together (deep windows)
     const bool small = g.ntiles < ie::encode_small_tiles();
-    const bool vec_ok = (reinterpret_cast<uintptr_t>(L.dy) % size_t(bpt * c->n) == 0) &&
-                        (L.stride % (bpt * c->n) == 0) && (L.nframes == 1 || L.frame_pitch % (bpt * c->n) == 0);
+    // every row piece starts on a multiple of m bytes: the base, the stride and (several frames) the pitch do
+    auto rows_aligned = [&L](size_t m) {
+        return reinterpret_cast<uintptr_t>(L.dy) % m == 0 && L.stride % m == 0 &&
+               (L.nframes == 1 || L.frame_pitch % m == 0);
+    };
+    const bool vec_ok = rows_aligned(size_t(bpt * c->n));  // a group's row: 16 bytes (4x4), 8 bytes (8x8)
+    const bool vec16 = rows_aligned(16);  // a 16-byte load or DMA of a row piece is naturally aligned
     int r;
     ie::EncArgs a{};
     a.y = L.dy;
@@ -34,7 +39,7 @@ int launch_chain(ie_ctx* c, const Launch& L) {
     a.ntiles = g.ntiles;
     a.rle = L.use_rle ? 1 : 0;
     a.segmented = L.segmented;
-    a.vec_ok = vec_ok ? 1 : 0;
+    a.vec_ok = (vec_ok ? ie::kVecGroup : 0) | (vec16 ? ie::kVec16 : 0);
     a.out = L.dout;
     a.out_pitch_words = L.segmented ? L.out_pitch / 4 : 0;
     a.start_bit = L.start_bit;

@@ -88,7 +88,7 @@ struct EncArgs {
     FastDiv div_frames, div_tpf, div_gpr;  // by nframes, tiles_per_frame, gpr
     int rle;
     int segmented;
-    int vec_ok;              // rows may be read with 16-/8-byte loads
+    int vec_ok;              // kVecGroup | kVec16 (below); 0: rows are read byte by byte
     uint32_t* out;           // 4-byte aligned, word w = stream bytes [4w, 4w+4)
     uint64_t out_pitch_words;
     uint64_t start_bit;
@@ -113,6 +113,11 @@ struct EncArgs {
     // [0, ceil(end/8)) -- header included -- ADDED to by the launch (the Huffman pass's counts)
     uint32_t* hist;
 };
+
+// EncArgs::vec_ok.  The frames' base, the row stride and (several frames) the frame pitch are all
+// multiples of ...
+constexpr int kVecGroup = 1;  // ... a group's row (4x4: 16 bytes, 8x8: 8): every group's row may be read with one load
+constexpr int kVec16 = 2;     // ... 16 bytes: what a 16-byte LDS DMA requires of its source (implies kVecGroup)
 
 constexpr int kStamps = 64;  // encode_kernel: [0, 16) by thread 0; encode4p_kernel: [4 waves][16] by each wave's lane 0
 // chain-state words per tile (the host allocates; ie_common.hpp kGran must not exceed it)

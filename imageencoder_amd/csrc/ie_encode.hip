@@ -140,10 +140,12 @@ __global__ IE_ENC_BOUNDS(N, EXACT) void encode_kernel(EncArgs a, const EncTables
     uint32_t seg[N][WPR];
     if constexpr (kLdsPix8) {
         // DMA when the wave's blocks pair up within rows (even bx): lanes 0-31 fetch row r, lanes
-        // 32-63 row r+1, 16 bytes = the row pieces of blocks 2c, 2c+1 (c = lane & 31) each
+        // 32-63 row r+1, 16 bytes = the row pieces of blocks 2c, 2c+1 (c = lane & 31) each.  Its
+        // 16-byte source must be 16-byte aligned (kVec16: base, stride and pitch are; the piece
+        // starts at an even block): rows that are only 8-byte aligned go through registers.
         const int wfirst = tif * TPB + (tid & ~63);                          // the wave's first block
         const int nwb = min(64, max(0, a.groups_per_frame - wfirst));        // its blocks in this frame
-        if (a.vec_ok && !(a.bx & 1) && nwb > 0) {
+        if ((a.vec_ok & kVec16) && !(a.bx & 1) && nwb > 0) {
             const int c = lane & 31, half = lane >> 5;
             const int bi = wfirst + 2 * c;                                    // block of this lane's piece
             const bool live = 2 * c < nwb;
@@ -154,7 +156,7 @@ __global__ IE_ENC_BOUNDS(N, EXACT) void encode_kernel(EncArgs a, const EncTables
                 if (live)
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + size_t(r + half) * a.stride),
                                                      (__attribute__((address_space(3))) void*)(pwave + r * kRowW), 16, 0, IE_PX_AUX8);
-        } else {  // odd bx / unaligned rows: through registers
+        } else {  // odd bx / rows not 16-byte aligned: through registers (8-byte loads, or bytes)
             load_tile<N, WPR, BPT>(a, g, seg);
 #pragma unroll
             for (int r = 0; r < N; r++) {
