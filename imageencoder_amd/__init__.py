@@ -131,6 +131,17 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ie_vstream_device.argtypes = [vp]
     L.ie_vstream_device.restype = C.c_void_p
     L.ie_vstream_close.argtypes = [vp]
+    if hasattr(L, "ie_vdec_open"):  # (absent from an older IE_LIB build under comparison)
+        ip = C.POINTER(C.c_int)
+        L.ie_vdec_open.restype = C.c_int
+        L.ie_vdec_open.argtypes = [vp, u8p, C.c_size_t, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.ie_vdec_next.restype = C.c_int
+        L.ie_vdec_next.argtypes = [vp, u8p, C.c_size_t, C.c_size_t, C.c_int, ip]
+        L.ie_vdec_info.restype = C.c_int
+        L.ie_vdec_info.argtypes = [vp, ip, ip, ip, u64p]
+        L.ie_vdec_close.restype = C.c_int
+        L.ie_vdec_close.argtypes = [vp]
     L.ie_huffman_decode.argtypes = [vp, u8p, C.c_size_t, C.c_uint64, vp, u8p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.ie_last_decode_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.ie_set_exact_parse.argtypes = [vp, C.c_int]
@@ -184,6 +195,14 @@ def load_host_library(path: str | None = None) -> C.CDLL:
         H.ieh_decode_images.restype = C.c_int64
         H.ieh_decode_images.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_uint64), C.c_int, C.c_int, vp, C.c_size_t,
                                         ip, ip]
+    if hasattr(H, "ieh_vdec_open"):  # (absent from an older IE_LIB build under comparison)
+        H.ieh_vdec_open.restype = C.c_int
+        H.ieh_vdec_open.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, ip, ip, ip, ip, ip,
+                                    C.POINTER(C.c_void_p)]
+        H.ieh_vdec_next.restype = C.c_int
+        H.ieh_vdec_next.argtypes = [vp, vp, C.c_size_t, ip]
+        H.ieh_vdec_close.restype = C.c_int
+        H.ieh_vdec_close.argtypes = [vp]
     H.ieh_huffman_encode.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
     H.ieh_huffman_decode.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, ip]
     H.ieh_huffman_table.argtypes = [vp, C.c_size_t, vp, C.POINTER(C.c_uint64)]
@@ -349,6 +368,56 @@ class VideoStream:
         if getattr(self, "v", None):
             self.c.L.ie_vstream_close(self.v)
             self.v = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VideoDecodeStream:
+    """ie_vdec_*: a video payload decoded in chunks of frames, handed out while later chunks still
+    decode (see include/ie_hip.h).  The frames in order equal :meth:`Codec.decode_gop`'s."""
+
+    def __init__(self, codec, stream, w, h, nframes, gop, merange, start_bit, rle, motioncomp, chunk_frames,
+                 length=None):
+        self.c = codec
+        self.w, self.h, self.nframes = w, h, nframes
+        self._in = stream  # (an aligned device stream is read in place until close)
+        v = C.c_void_p()
+        codec._chk(codec.L.ie_vdec_open(codec.h, _ptr(stream), _nbytes(stream) if length is None else length, start_bit,
+                                        w, h, nframes, gop, merange, int(rle), int(motioncomp), chunk_frames,
+                                        C.byref(v)))
+        self.v = v
+
+    def next(self, out, max_frames: int, stride: int | None = None, frame_pitch: int | None = None) -> int:
+        """Up to ``max_frames`` frames into ``out`` (host or device; frame i of the call at
+        ``i * frame_pitch``); returns how many, 0 after the last.  A stream that ends early raises
+        :class:`IEError` (IE_EFORMAT) whose ``got`` is the number of whole frames written first."""
+        stride = self.w if stride is None else stride
+        frame_pitch = stride * self.h if frame_pitch is None else frame_pitch
+        got = C.c_int(0)
+        r = self.c.L.ie_vdec_next(self.v, _ptr(out), stride, frame_pitch, max_frames, C.byref(got))
+        if r != IE_OK:
+            e = IEError(r, self.c.L.ie_last_error(self.c.h).decode())
+            e.got = int(got.value)
+            raise e
+        return int(got.value)
+
+    def info(self) -> dict:
+        """chunk_frames, chunks_enqueued, chunks_delivered, end_bit (2**64 - 1 until the last frame is out)."""
+        k, e, d, end = C.c_int(0), C.c_int(0), C.c_int(0), C.c_uint64(0)
+        self.c._chk(self.c.L.ie_vdec_info(self.v, C.byref(k), C.byref(e), C.byref(d), C.byref(end)))
+        return dict(chunk_frames=int(k.value), chunks_enqueued=int(e.value), chunks_delivered=int(d.value),
+                    end_bit=int(end.value))
+
+    def close(self):
+        if getattr(self, "v", None):
+            if getattr(self.c, "h", None):
+                self.c.L.ie_vdec_close(self.v)
+            self.v = None
+            self._in = None
 
     def __del__(self):
         try:
@@ -581,6 +650,15 @@ class Codec:
         encoded in chunks of whole groups of pictures (the stream equals encode_gop's)."""
         return VideoStream(self, w, h, head, start_bit, max_frames, stride, frame_pitch, rle, mode, gop, merange)
 
+    def open_video_decode(self, stream, w: int, h: int, nframes: int, gop: int = 1, merange: int = 0,
+                          start_bit: int = 0, rle: bool = True, motioncomp: bool = True, chunk_frames: int = 0,
+                          length: int | None = None) -> "VideoDecodeStream":
+        """ie_vdec_open: the payload ``stream`` (host or device) decoded in chunks of
+        ``chunk_frames`` frames (0: IE_CHUNK_MB's pixel target) through two device slots; the
+        frames that :meth:`VideoDecodeStream.next` hands out equal :meth:`decode_gop`'s."""
+        return VideoDecodeStream(self, stream, w, h, nframes, gop, merange, start_bit, rle, motioncomp, chunk_frames,
+                                 length)
+
     def end_bits_into(self, dst, count: int = 1):
         """Stream-ordered device copy of the last encode's end bit(s) (one per chain) into the
         device tensor ``dst`` (uint64/int64): no host read-back."""
@@ -791,6 +869,38 @@ class Codec:
         r = self._host_chk(H.ieh_decode_video(self.h, src.ctypes.data, src.size, n, out.ctypes.data, cap, C.byref(w),
                                               C.byref(h), C.byref(f)))
         return out[:r], (w.value, h.value, f.value)
+
+    def iter_video_file(self, data: bytes, n: int, motioncomp: bool = True, chunk_frames: int = 0):
+        """The frames of an encoded video file chunk by chunk (ieh_vdec_*): yields
+        ``(frames_in_chunk, ndarray)``, the array holding those frames in the file's layout (Y, then
+        w*h/2 bytes of 0x80 each); all of them in order are :meth:`decode_video_file`'s bytes."""
+        H = load_host_library()
+        src = np.frombuffer(data, dtype=np.uint8).copy()
+        w, h, f, gop, mer = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        v = C.c_void_p()
+        self._host_chk(H.ieh_vdec_open(self.h, src.ctypes.data, src.size, n, int(motioncomp), chunk_frames, C.byref(w),
+                                       C.byref(h), C.byref(f), C.byref(gop), C.byref(mer), C.byref(v)))
+        self.n = n
+        try:
+            pitch = w.value * h.value + w.value * h.value // 2
+            if chunk_frames > 0:
+                k = chunk_frames
+            else:
+                mb = os.environ.get("IE_CHUNK_MB")
+                target = int(float(mb) * 1048576) if mb and float(mb) > 0 else 8 << 20
+                k = max(1, target // max(1, w.value * h.value))
+            k = max(1, min(k, f.value))
+            done = 0
+            while done < f.value and pitch:
+                buf = np.zeros(k * pitch, dtype=np.uint8)
+                got = C.c_int(0)
+                self._host_chk(H.ieh_vdec_next(v, buf.ctypes.data, buf.size, C.byref(got)))
+                if got.value == 0:
+                    break
+                done += got.value
+                yield got.value, buf[: got.value * pitch]
+        finally:
+            H.ieh_vdec_close(v)
 
     def huffman_encode_device(self, data, nbytes: int, out) -> int:
         """Huffman pass from device ``data[:nbytes]`` into device ``out``; returns output bytes."""

@@ -175,7 +175,7 @@ int main(int argc, char* argv[]) {
                                       "' to uint16_t.");
                 return 5;
             }
-            dc::VideoDecoder dec(encfile, decfile, motioncomp != 0, n);
+            dc::VideoDecoder dec(encfile, decfile, motioncomp != 0, n, true);  // frames written as they decode
             if (dec.process()) {
                 dec.saveResult();
                 elapsed(start);

@@ -248,19 +248,29 @@ static bool parse_header(const uint8_t* src, size_t len, size_t start, int n, bo
 // Video frames come out as Y followed by w*h/2 bytes of UV fill.
 // cap: the caller's pixel capacity -- a smaller one returns IE_ECAP right after the header (sh
 // filled in), before the payload is decoded
-static int decode_file(ie_ctx* c, const uint8_t* enc, size_t len, int n, bool video, StreamHeader& sh,
-                       std::vector<uint8_t>& pix, std::string& err, size_t cap = SIZE_MAX, bool motioncomp = true) {
+// The front half of every file decode: the Huffman pass (dec: its output when the file has a
+// dictionary), the settings header, ie_set_quant.  *src / *srclen: the stream the payload is in.
+static int decode_front(ie_ctx* c, const uint8_t* enc, size_t len, int n, bool video, StreamHeader& sh,
+                        std::vector<uint8_t>& dec, const uint8_t** src, size_t* srclen, std::string& err) {
     if (!c) return (err = "no GPU context", IE_EHIP);
-    std::vector<uint8_t> dec;
     bool pass = false;
     size_t start = 0;
     if (int r = algo::Huffman::decode(c, enc, len, dec, pass, start))
         return (err = (r == IE_EFORMAT ? std::string("malformed Huffman stream") : std::string(ie_last_error(c))), r);
-    const uint8_t* src = pass ? enc : dec.data();
-    const size_t srclen = pass ? len : dec.size();
-    if (!parse_header(src, srclen, start, n, video, sh)) return (err = "stream shorter than its header", IE_EFORMAT);
+    *src = pass ? enc : dec.data();
+    *srclen = pass ? len : dec.size();
+    if (!parse_header(*src, *srclen, start, n, video, sh)) return (err = "stream shorter than its header", IE_EFORMAT);
+    if (int r = ie_set_quant(c, sh.q.data(), n)) return (err = ie_last_error(c), r);
+    return IE_OK;
+}
+
+static int decode_file(ie_ctx* c, const uint8_t* enc, size_t len, int n, bool video, StreamHeader& sh,
+                       std::vector<uint8_t>& pix, std::string& err, size_t cap = SIZE_MAX, bool motioncomp = true) {
+    std::vector<uint8_t> dec;
+    const uint8_t* src = nullptr;
+    size_t srclen = 0;
     int r;
-    if ((r = ie_set_quant(c, sh.q.data(), n))) return (err = ie_last_error(c), r);
+    if ((r = decode_front(c, enc, len, n, video, sh, dec, &src, &srclen, err))) return r;
     const size_t fbytes = size_t(sh.w) * sh.h;
     const size_t pitch = video ? fbytes + fbytes / 2 : fbytes;
     if (pitch * size_t(sh.frames) > cap) return IE_ECAP;
@@ -276,6 +286,59 @@ static int decode_file(ie_ctx* c, const uint8_t* enc, size_t len, int n, bool vi
                               pitch, nullptr)))
         return (err = ie_last_error(c), r);
     return IE_OK;
+}
+
+}  // namespace dc
+
+// A video file decoded chunk by chunk (ieh_vdec_*): decode_file's front half, then an ie_vdec over
+// the payload.  The Huffman-decoded stream (if any) is the decoder's own copy on the device, so
+// nothing of the file is kept on the host after open.
+struct ieh_vdec {
+    ie_ctx* c = nullptr;
+    ie_vdec* v = nullptr;
+    dc::StreamHeader sh;
+    size_t done = 0;  // frames handed out
+};
+
+namespace dc {
+
+static int vdec_open(ie_ctx* c, const uint8_t* enc, size_t len, int n, bool motioncomp, int chunk_frames,
+                     ieh_vdec** out, std::string& err) {
+    std::unique_ptr<ieh_vdec> d(new ieh_vdec());
+    d->c = c;
+    std::vector<uint8_t> dec;
+    const uint8_t* src = nullptr;
+    size_t srclen = 0;
+    int r;
+    if ((r = decode_front(c, enc, len, n, true, d->sh, dec, &src, &srclen, err))) return r;
+    const StreamHeader& sh = d->sh;
+    if (sh.w && sh.h && sh.frames &&
+        (r = ie_vdec_open(c, src, srclen, sh.payload_bit, sh.w, sh.h, sh.frames, sh.gop, sh.merange, sh.rle,
+                          motioncomp ? 1 : 0, chunk_frames, &d->v)))
+        return (err = ie_last_error(c), r);
+    *out = d.release();
+    return IE_OK;
+}
+
+// Whole frames in the file's layout -- Y, then w*h/2 bytes of 0x80 (Frame.cpp:121-124) -- as many as
+// cap holds.  An error leaves *got at the frames written before it.
+static int vdec_next(ieh_vdec* d, uint8_t* out, size_t cap, int* got, std::string& err) {
+    *got = 0;
+    const size_t fbytes = size_t(d->sh.w) * d->sh.h, pitch = fbytes + fbytes / 2;
+    if (!d->v || !pitch) return IE_OK;
+    const size_t room = std::min<size_t>(cap / pitch, size_t(d->sh.frames) - d->done);
+    if (!room) return IE_OK;
+    const int r = ie_vdec_next(d->v, out, size_t(d->sh.w), pitch, int(std::min<size_t>(room, size_t(INT32_MAX))), got);
+    for (int i = 0; i < *got; i++) std::memset(out + size_t(i) * pitch + fbytes, 0x80, pitch - fbytes);
+    d->done += size_t(*got);
+    if (r) err = ie_last_error(d->c);
+    return r;
+}
+
+static void vdec_close(ieh_vdec* d) {
+    if (!d) return;
+    ie_vdec_close(d->v);
+    delete d;
 }
 
 // A batch of image files with the same settings into pixels, w*h bytes per image back to back in
@@ -508,12 +571,60 @@ bool VideoEncoder::process() {
 
 // ------------------------------------------------------------------------------- VideoDecoder
 VideoDecoder::VideoDecoder(const std::string& source_file, const std::string& dest_file, const bool& mc,
-                           int block_size)
-    : VideoProcessor(source_file, dest_file, mc), n_(block_size ? block_size : block_size_from_env()) {}
+                           int block_size, bool stream_to_file)
+    : VideoProcessor(source_file, dest_file, mc), n_(block_size ? block_size : block_size_from_env()),
+      stream_to_file_(stream_to_file) {}
+
+// The frames written to dest_file as their chunks arrive: two page-locked buffers of a chunk of
+// frames in turn, so the write of one chunk runs while the next one crosses.  A failure removes the
+// partial file: a failed run leaves no output, as before.
+bool VideoDecoder::processToFile() {
+    ie_ctx* c = Device::get();
+    ieh_vdec* d = nullptr;
+    if (vdec_open(c, raw.data(), raw.size(), n_, motioncomp, 0, &d, err_) != IE_OK) return false;
+    const StreamHeader sh = d->sh;
+    std::vector<uint8_t>().swap(raw);  // (the decoder has its own copy of the stream)
+    const size_t fbytes = size_t(sh.w) * sh.h, pitch = fbytes + fbytes / 2;
+    int K = 1;
+    if (d->v) ie_vdec_info(d->v, &K, nullptr, nullptr, nullptr);
+    K = std::max(1, std::min(K, sh.frames));
+    FILE* f = std::fopen(dest_file.c_str(), "wb");
+    bool ok = f != nullptr;
+    if (!ok) err_ = "Could not write '" + dest_file + "'";
+    void* buf = nullptr;
+    if (ok && pitch && ie_host_alloc(c, size_t(K) * pitch, &buf) != IE_OK) ok = (err_ = ie_last_error(c), false);
+    size_t frames = 0;
+    while (ok && frames < size_t(sh.frames) && pitch) {
+        int got = 0;
+        if (vdec_next(d, static_cast<uint8_t*>(buf), size_t(K) * pitch, &got, err_) != IE_OK || got == 0) {
+            if (err_.empty()) err_ = "stream ends before the last block";
+            ok = false;
+        } else if (std::fwrite(buf, pitch, size_t(got), f) != size_t(got)) {
+            ok = (err_ = "Could not write '" + dest_file + "'", false);
+        }
+        frames += size_t(got);
+    }
+    if (buf) ie_host_free(c, buf);
+    vdec_close(d);
+    if (f && std::fclose(f) != 0 && ok) ok = (err_ = "Could not write '" + dest_file + "'", false);
+    if (!ok && f) std::remove(dest_file.c_str());
+    if (!ok) return false;
+    width = uint16_t(sh.w);
+    height = uint16_t(sh.h);
+    gop = uint16_t(sh.gop);
+    merange = uint16_t(sh.merange);
+    return true;
+}
+
+void VideoDecoder::saveResult() const {
+    if (!stream_to_file_) return VideoProcessor::saveResult(false);
+    util::Logger::WriteLn("[VideoProcessor] Saved file at: " + dest_file);  // (process() wrote it)
+}
 
 bool VideoDecoder::process() {
     if (!err_.empty()) return false;
     util::Logger::WriteLn("[VideoDecoder] Processing video...");
+    if (stream_to_file_) return processToFile();
     StreamHeader sh;
     if (decode_file(Device::get(), raw.data(), raw.size(), n_, true, sh, result_, err_, SIZE_MAX, motioncomp) != IE_OK)
         return false;
@@ -831,6 +942,38 @@ int64_t ieh_decode_video(ie_ctx* c, const uint8_t* enc, size_t len, int n, uint8
     if (r) return r;
     std::memcpy(out, pix.data(), pix.size());
     return int64_t(pix.size());
+}
+
+int ieh_vdec_open(ie_ctx* c, const uint8_t* enc, size_t len, int n, int motioncomp, int chunk_frames, int* w, int* h,
+                  int* frames, int* gop, int* merange, ieh_vdec** out) {
+    if (!c || !enc || !out) return IE_EINVAL;
+    *out = nullptr;
+    std::string err;
+    ieh_vdec* d = nullptr;
+    const int r = dc::vdec_open(c, enc, len, n, motioncomp != 0, chunk_frames, &d, err);
+    if (r) return (ie_set_error(c, err.c_str()), r);
+    if (w) *w = d->sh.w;
+    if (h) *h = d->sh.h;
+    if (frames) *frames = d->sh.frames;
+    if (gop) *gop = d->sh.gop;
+    if (merange) *merange = d->sh.merange;
+    *out = d;
+    return IE_OK;
+}
+
+int ieh_vdec_next(ieh_vdec* v, uint8_t* out, size_t cap, int* got) {
+    if (!v || !got) return IE_EINVAL;
+    *got = 0;
+    if (!out) return (ie_set_error(v->c, "ieh_vdec_next: null out"), IE_EINVAL);
+    std::string err;
+    const int r = dc::vdec_next(v, out, cap, got, err);
+    if (r) ie_set_error(v->c, err.c_str());
+    return r;
+}
+
+int ieh_vdec_close(ieh_vdec* v) {
+    dc::vdec_close(v);
+    return IE_OK;
 }
 
 int64_t ieh_huffman_encode_device(ie_ctx* c, const uint8_t* din, size_t n, uint8_t* dout, size_t cap) {

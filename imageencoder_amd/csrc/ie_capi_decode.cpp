@@ -60,15 +60,11 @@ ie::DecArgs dec_args(const ie_ctx* c, int w, int h, int use_rle, size_t stride) 
 #ifndef IE_GOP_CAPC
 #define IE_GOP_CAPC 1  // 0: (A/B builds) gop decode chunks sized by the I-frame bound alone
 #endif
-// Chunk plan of a record span (span bits from the first record, nblocks records).
-struct RecPlan {
-    uint64_t C;       // chunk bits
-    int nchunks;
-    size_t tab_rows;  // rows of D entries: the chunks' tables and every level's composites
-    int levels;
-};
-int plan_chunks(ie_ctx* c, uint64_t span, uint64_t nblocks, uint64_t cmax, RecPlan* plan) {
-    const int n = c->n;
+
+}  // namespace
+
+// Chunk plan of a record span (RecPlan, ie_ctx.hpp) for block size n.
+int iec::plan_chunks(ie_ctx* c, int n, uint64_t span, uint64_t nblocks, uint64_t cmax, RecPlan* plan) {
     // chunking: about R records per chunk (IE_DEC_R; default 24 for 4x4, 28 for 8x8: measured
     // with 32-table composition groups on 4K noise / mixed / gradient / flat frames and the
     // reference's ex1 / ex4 -- 4x4 against 16, 24, 32, 48: ex4 126 -> 115 us, mixed 197 -> 191 us,
@@ -92,31 +88,34 @@ int plan_chunks(ie_ctx* c, uint64_t span, uint64_t nblocks, uint64_t cmax, RecPl
     *plan = {C, int(nch), tab_rows, levels};
     return IE_OK;
 }
+
 // Scratch of one image under a plan, and of `batch` images side by side.  Per image: its tables and
 // composites (img_tab entries, a multiple of 8 so that every image's start 16-byte aligned) and
 // kRecPosCap positions per chunk; in d_walk, as 32-bit words, one array per kind holding every
 // image's part in turn -- record bases and counts [nchunks], count workgroups' totals [nwg],
 // top-level entries [G] -- then the speculative exits [nchunks] (single stream only).  Every
 // array starts on an 8-byte word.
+namespace {
 struct DecScratch {
     size_t img_tab, nwg, img_bytes;
     int seg;
 };
-DecScratch dec_scratch_size(const ie_ctx* c, const RecPlan& pl) {
+DecScratch dec_scratch_size(int n, const RecPlan& pl) {
     DecScratch s;
-    const size_t nch = size_t(pl.nchunks), G = size_t(ie::rec_group_chunks(c->n));
+    const size_t nch = size_t(pl.nchunks), G = size_t(ie::rec_group_chunks(n));
     s.seg = ie::rec_count_seg(uint32_t(pl.C));
     s.nwg = (nch + 4 * size_t(s.seg) - 1) / (4 * size_t(s.seg));
-    s.img_tab = (pl.tab_rows * size_t(ie::rec_entry_span(c->n)) + 7) / 8 * 8;
+    s.img_tab = (pl.tab_rows * size_t(ie::rec_entry_span(n)) + 7) / 8 * 8;
     s.img_bytes = s.img_tab * 2 + nch * ie::kRecPosCap * 2 + (2 * nch + s.nwg + G) * 4;
     return s;
 }
+}  // namespace
 // Grows the parse buffers for `batch` images and fills a's chunking fields, scratch pointers and
 // batch strides (the single-stream kernels ignore the strides).  The record stream's own fields
 // (words, nbits, start_bit, dstart, total, end_out) are the caller's.  *spec (optional): the exits.
-int dec_scratch(ie_ctx* c, const RecPlan& pl, size_t batch, ie::RecParseArgs& a, uint32_t** spec = nullptr) {
-    const DecScratch s = dec_scratch_size(c, pl);
-    const size_t nch = size_t(pl.nchunks), G = size_t(ie::rec_group_chunks(c->n));
+int iec::dec_scratch(ie_ctx* c, int n, const RecPlan& pl, size_t batch, ie::RecParseArgs& a, uint32_t** spec) {
+    const DecScratch s = dec_scratch_size(n, pl);
+    const size_t nch = size_t(pl.nchunks), G = size_t(ie::rec_group_chunks(n));
     auto even = [](size_t words32) { return (words32 + 1) / 2 * 2; };
     const size_t cnt_at = even(batch * nch), wg_at = cnt_at + even(batch * nch), e_at = wg_at + even(batch * s.nwg);
     const size_t spec_at = e_at + even(batch * G), end = spec_at + (spec ? even(nch) : 0);
@@ -141,6 +140,8 @@ int dec_scratch(ie_ctx* c, const RecPlan& pl, size_t batch, ie::RecParseArgs& a,
     a.img_E = uint32_t(G);
     return IE_OK;
 }
+
+namespace {
 
 // Profiling of the single-stream record decode (IE_PROFILE builds, tools/prof_decode.py and
 // tools/dec_stamps.py): host-side phase times and the table pass's per-wave stamps (IE_DEC_STAMPS =
@@ -200,7 +201,6 @@ struct DecProfile {
 };
 #endif
 
-constexpr uint64_t kMaxChunkBits = uint64_t(1) << 15;  // (16-bit record positions)
 constexpr size_t kDecBatchBytes = size_t(1) << 30;    // ie_decode_images: scratch of one sub-batch
 
 }  // namespace
@@ -225,8 +225,8 @@ int ie_decode_frames(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bi
     RecPlan pl{};
     ie::RecParseArgs pa{};
     uint32_t* spec_exits = nullptr;
-    if ((r = plan_chunks(c, nbits - start_bit, nblocks, kMaxChunkBits, &pl))) return r;
-    if ((r = dec_scratch(c, pl, 1, pa, &spec_exits))) return r;
+    if ((r = plan_chunks(c, n, nbits - start_bit, nblocks, kMaxChunkBits, &pl))) return r;
+    if ((r = dec_scratch(c, n, pl, 1, pa, &spec_exits))) return r;
     int levels = pl.levels;
     bool out_dev;
     uint8_t* dpix;
@@ -318,13 +318,13 @@ int ie_decode_images(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64
     const int n = c->n;
     const uint64_t nblocks = uint64_t(w / n) * (h / n);
     RecPlan pl{};
-    if ((r = plan_chunks(c, max_bits - start_bit, nblocks, kMaxChunkBits, &pl))) return r;
-    size_t batch = std::max<size_t>(1, kDecBatchBytes / dec_scratch_size(c, pl).img_bytes);
+    if ((r = plan_chunks(c, n, max_bits - start_bit, nblocks, kMaxChunkBits, &pl))) return r;
+    size_t batch = std::max<size_t>(1, kDecBatchBytes / dec_scratch_size(n, pl).img_bytes);
     if (const char* eb = getenv("IE_DEC_BATCH_MAX"))  // (read on every call: a limit in images, only ever lower)
         if (atoi(eb) > 0) batch = std::min<size_t>(batch, size_t(atoi(eb)));
     batch = std::min<size_t>(batch, size_t(count));
     ie::RecParseArgs pa{};
-    if ((r = dec_scratch(c, pl, batch, pa))) return r;
+    if ((r = dec_scratch(c, n, pl, batch, pa))) return r;
     if ((r = c->d_imgbits.reserve(c, size_t(count)))) return r;
     if ((r = c->h_imgres.reserve(c, 3 * std::max<size_t>(size_t(count), 16)))) return r;
     // the stream lengths: through pinned memory into a device array (every workgroup reads its
@@ -449,8 +449,8 @@ int ie_decode_gop(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bit, 
     // record is valid there too; chunks dense with them take the re-walk))
     const uint64_t min_rec = use_rle ? 4u : uint64_t(4 + n * n);
     const uint64_t cmax = (gop > 1 && IE_GOP_CAPC) ? uint64_t(ie::kRecPosCap) * min_rec : kMaxChunkBits;
-    if ((r = plan_chunks(c, rec_bound, nblocks, cmax, &pl))) return r;
-    if ((r = dec_scratch(c, pl, 1, pa))) return r;
+    if ((r = plan_chunks(c, n, rec_bound, nblocks, cmax, &pl))) return r;
+    if ((r = dec_scratch(c, n, pl, 1, pa))) return r;
     ie::DecArgs da = dec_args(c, w, h, use_rle, stride);
     da.nframes = 1;
     pa.words = reinterpret_cast<const uint32_t*>(words);

@@ -124,10 +124,6 @@ int pipe_get(ie_ctx* c, Pipe*& P) {
 
 // frames per chunk: ~8 MiB of pixels (at least 1, at most kMaxChunk), and at least two chunks
 // (IE_CHUNK_MB overrides the target: a tuning aid, the output does not depend on it)
-size_t chunk_target() {
-    const char* e = getenv("IE_CHUNK_MB");
-    return (e && atof(e) > 0) ? size_t(atof(e) * 1048576.0) : size_t(8) << 20;
-}
 int chunk_frames(size_t frame_bytes, int nframes) {
     int k = int(std::max<size_t>(1, chunk_target() / std::max<size_t>(1, frame_bytes)));
     k = std::min(k, kMaxChunk);
@@ -428,6 +424,11 @@ int ie_vstream_close(ie_vstream* v) {
 }  // extern "C"
 
 namespace iec {
+
+size_t chunk_target() {
+    const char* e = getenv("IE_CHUNK_MB");
+    return (e && atof(e) > 0) ? size_t(atof(e) * 1048576.0) : size_t(8) << 20;
+}
 
 void pipe_free(Pipe* p) { delete p; }  // (~ie_pipe waits for its two streams first)
 

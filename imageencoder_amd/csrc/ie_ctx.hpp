@@ -33,6 +33,7 @@
 #endif
 
 struct ie_pipe;  // streamed host path (ie_capi_stream.cpp)
+struct ie_vdec;  // streamed video decode (ie_capi_vdec.cpp)
 struct ie_ctx;
 
 namespace iec {
@@ -222,6 +223,7 @@ struct ie_ctx {
     int spec_warm = 0;                 // ie_set_spec_warm(ctx, w): w warm-up chunks (<= 8)
     iec::Buf<unsigned long long> d_first;   // [256]
     ie_pipe* pipe = nullptr;           // streamed host path of image batches (created on first use)
+    ie_vdec* vdec = nullptr;           // the open streamed video decoder (one per context; its owner closes it)
     // P-frame videos (ie_encode_gop): reconstructed frames (two, alternating), the prediction
     // error's coefficients and record lengths, the scan's tile sums, the frames' bit positions
     iec::Buf<uint8_t> d_gop_rec;
@@ -420,7 +422,23 @@ int launch_gop_wave(ie_ctx* c, const GopWave& W, const uint8_t* wy, int w, int h
                     int gw, int nfw, int merange, int use_rle, int mode, uint32_t* dout, uint64_t start_bit,
                     const uint64_t* base_dev, uint64_t* fpos);
 
+// ---- ie_capi_decode.cpp: the record parse's chunk plan and scratch (ie_capi_vdec.cpp plans its
+// chunks of frames with them)
+constexpr uint64_t kMaxChunkBits = uint64_t(1) << 15;  // (16-bit record positions)
+// Chunk plan of a record span (span bits from the first record, nblocks records).
+struct RecPlan {
+    uint64_t C;       // chunk bits
+    int nchunks;
+    size_t tab_rows;  // rows of D entries: the chunks' tables and every level's composites
+    int levels;
+};
+// n: the block size of the stream (the context's, or the one a streamed decoder took at open)
+int plan_chunks(ie_ctx* c, int n, uint64_t span, uint64_t nblocks, uint64_t cmax, RecPlan* plan);
+int dec_scratch(ie_ctx* c, int n, const RecPlan& pl, size_t batch, ie::RecParseArgs& a, uint32_t** spec = nullptr);
+
 // ---- ie_capi_stream.cpp: host frames in, host streams out
+// IE_CHUNK_MB's pixel target of a streamed chunk (default 8 MiB; ie_vstream and ie_vdec)
+size_t chunk_target();
 int streamed_images(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,
                     int use_rle, int mode, uint8_t* out, size_t out_pitch, uint64_t start_bit, uint64_t* end_bits);
 int streamed_frames(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,

@@ -24,6 +24,8 @@
 //                      per chunk walks from a warm-up distance before it; the count pass verifies
 //                      every exit and the decode writes nothing if one was wrong.
 //   gop_init_kernel    the position and total arrays of a device-chained video decode.
+//   gop_cont_kernel    the same arrays for a chunk of frames that starts where an earlier chunk
+//                      ended (ie_vdec): the first bit is read from that chunk's end word.
 #include <algorithm>
 #include <cstdlib>
 
@@ -783,6 +785,21 @@ __global__ void gop_init_kernel(uint64_t* pos, uint64_t* tot, int n, uint64_t st
 }
 void launch_gop_init(uint64_t* pos, uint64_t* tot, int n, uint64_t start, hipStream_t s) {
     hipLaunchKernelGGL(gop_init_kernel, dim3(1), dim3(256), 0, s, pos, tot, n, start);
+}
+
+// Chain continuation (ie_vdec): the arrays of a chunk of frames whose first bit is the end bit an
+// earlier chunk's last decode wrote -- read here, on the device, so no host round trip separates
+// two chunks.  ~0 (that chunk found no end: a truncated stream) is passed on: the span of every
+// launch that starts there is empty (rec_span).
+__global__ void gop_cont_kernel(uint64_t* pos, uint64_t* tot, int n, const uint64_t* prev_end) {
+    const uint64_t start = *prev_end;
+    for (int i = threadIdx.x; i <= n; i += blockDim.x) {
+        pos[i] = i ? ~0ull : start;
+        if (i < n) tot[i] = 0;
+    }
+}
+void launch_gop_continue(uint64_t* pos, uint64_t* tot, int n, const uint64_t* prev_end, hipStream_t s) {
+    hipLaunchKernelGGL(gop_cont_kernel, dim3(1), dim3(256), 0, s, pos, tot, n, prev_end);
 }
 
 void launch_rec_spec_decode(const RecParseArgs& a, const DecArgs& d, int n, hipStream_t s) {

@@ -392,6 +392,8 @@ void launch_gop_splice(const GopSplice& a, hipStream_t s);
 // vector copied into place
 // gop decode: pos[0] = start, pos[1..n] = ~0 (no end yet), tot[0..n) = 0
 void launch_gop_init(uint64_t* pos, uint64_t* tot, int n, uint64_t start, hipStream_t s);
+// the same arrays with pos[0] = *prev_end (device: the end word of the chunk of frames before)
+void launch_gop_continue(uint64_t* pos, uint64_t* tot, int n, const uint64_t* prev_end, hipStream_t s);
 // dstart non-null: the vectors start at *dstart (device, an earlier launch's end bit) in place of
 // start_bit; a macroblock whose vector lies past nbits copies nothing (the caller reports it)
 void launch_pframe_mvcopy(const uint8_t* stream, uint64_t start_bit, const uint64_t* dstart, uint64_t nbits, int mv_bits,

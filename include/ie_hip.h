@@ -454,6 +454,49 @@ int ie_decode_gop(ie_ctx* ctx, const uint8_t* in, size_t len, uint64_t start_bit
                   int gop, int merange, int use_rle, int motioncomp, uint8_t* out, size_t stride,
                   size_t frame_pitch, uint64_t* end_bit);
 
+/* Streamed video decode (the mirror of ie_vstream; VideoDecoder.cpp:28-58 for frames that leave as
+ * they are decoded): ie_decode_gop's payload handed out in chunks of frames.  open: the stream `in`
+ * (len bytes, host or device) with ie_decode_gop's arguments; gop <= 1 means every frame is an
+ * I-frame.  chunk_frames: frames per chunk; 0 picks max(1, target / (w*h)) with IE_CHUNK_MB's pixel
+ * target (default 8 MiB, read at open); the output does not depend on it.  next: the next frames,
+ * at most max_frames of them (*got), frame i of the call at out + i*frame_pitch, its row r at
+ * + r*stride, only the w bytes of a row written (out host or device; stride >= w, frame_pitch
+ * covers a frame when max_frames > 1).  After the last frame next returns IE_OK with *got = 0.
+ * info: the frames per chunk, the chunks enqueued and delivered so far (enqueued <= delivered + 2
+ * at all times) and the end bit, UINT64_MAX until the last frame is out.  For ANY chunk_frames >= 1
+ * and ANY partition of the video into next calls, the frames in order equal, byte for byte, what
+ * ie_decode_gop writes for the whole stream with the same arguments, and the end bit equals its.
+ *  - Checks at open: ie_decode_gop's in its order with its codes (IE_ENOQUANT, dimensions, merange
+ *    in [0, 32767], P-frames only for W % 16 == 0 && H % 16 == 0, start_bit <= 8*len), then
+ *    chunk_frames < 0 and a second open decoder on the context (one at a time): IE_EINVAL.
+ *  - Pipeline: two device slots of chunk_frames frames.  open enqueues chunks 0 and 1; the next that
+ *    hands out the last frame of chunk k enqueues chunk k+2 into the slot just freed (a host out:
+ *    once chunk k's D2H is complete; a device out: behind the copy in stream order) before it waits
+ *    for anything further, so chunk k+1 decodes while chunk k's frames cross.  A chunk starts at the
+ *    end bit of the chunk before it, read on the device: one host synchronisation per chunk, the
+ *    read of its positions and record totals.  With gop <= 1 a chunk is one exact parse of
+ *    chunk_frames frames; with gop > 1 the per-frame launches of ie_decode_gop, a chunk's first
+ *    P-frame reading its reference from the other slot.  A host out is written through a D2H stream
+ *    of the decoder's own: directly when page-locked (ie_host_alloc), else through pinned staging.
+ *  - Ownership: a host `in` (or an unaligned device one) is copied at open and may be freed when
+ *    open returns; a 16-byte aligned device `in` is read in place and must stay valid until close.
+ *    The decoder keeps its own copy of the quantisation tables and block size as they were at open,
+ *    its positions and its slots: ie_set_quant with another matrix, or any other decode or encode
+ *    on the context between two next calls, changes nothing.  Device memory: the two slots and the
+ *    stream, whatever nframes is.  The context's stream must stay the same from open to close.
+ *  - A stream that ends inside frame f (its vectors or its records): the next that reaches f hands
+ *    out the frames before f (*got), returns IE_EFORMAT with ie_decode_gop's message, and every
+ *    later next returns IE_EFORMAT with *got = 0.  (gop <= 1: the whole frames of a chunk are its
+ *    record total / blocks per frame.)  max_frames < 1: IE_EINVAL.
+ *  - close waits for the chunks still decoding; call it before ie_destroy. */
+typedef struct ie_vdec ie_vdec;
+int ie_vdec_open(ie_ctx* ctx, const uint8_t* in, size_t len, uint64_t start_bit, int w, int h, int nframes,
+                 int gop, int merange, int use_rle, int motioncomp, int chunk_frames, ie_vdec** out);
+int ie_vdec_next(ie_vdec* v, uint8_t* out, size_t stride, size_t frame_pitch, int max_frames, int* got);
+int ie_vdec_info(const ie_vdec* v, int* chunk_frames, int* chunks_enqueued, int* chunks_delivered,
+                 uint64_t* end_bit);
+int ie_vdec_close(ie_vdec* v);
+
 /* Chunks and composition levels of the last ie_decode_frames call's exact parse (after
  * ie_decode_images: the chunks per image) (diagnostics: the
  * stream is cut into chunks of about 32 (4x4) / 16 (8x8) records, each tabulated over every entry

@@ -11,7 +11,8 @@
 //   algo::Huffman                 Huffman.hpp:109-142       byte Huffman post-pass (tree on the host)
 //   dc::ImageEncoder/ImageDecoder ImageEncoder.hpp, ImageDecoder.hpp
 //   dc::VideoEncoder/VideoDecoder VideoEncoder.hpp, VideoDecoder.hpp (any gop: I-frames and
-//                                 P-frames with motion compensation on / off, ie_decode_gop)
+//                                 P-frames with motion compensation on / off, ie_decode_gop; or
+//                                 streamed to the output file, ie_vdec)
 // Every block-level operation (DCT, quantisation, RLE, bit packing, the inverse) runs on the
 // GPU; there is no CPU fallback.
 #pragma once
@@ -250,7 +251,9 @@ private:
 // (VideoEncoder.cpp:22-107, Frame.cpp:31-45).  Any gop: frame f is an I-frame when f % gop == 0,
 // every other frame a P-frame (motion search + coded prediction error).  The encoder streams the
 // file through an ie_vstream for every gop (with gop > 1 in chunks of whole groups of pictures,
-// ie_vstream_open_gop) and never holds the whole video; the decoder reads the file whole.
+// ie_vstream_open_gop) and never holds the whole video; the decoder reads the ENCODED file whole
+// and, with stream_to_file (the decoder command line), hands the decoded frames to the output file
+// chunk by chunk through an ie_vdec, so it never holds the decoded video either.
 class VideoProcessor {
 public:
     VideoProcessor(const std::string& source_file, const std::string& dest_file, const uint16_t& width,
@@ -307,15 +310,20 @@ private:
 };
 
 // dc::VideoDecoder (VideoDecoder.hpp): frames of Y + W*H/2 bytes of 0x80 (Frame.cpp:121-124).
+// stream_to_file: process() decodes through an ie_vdec and writes dest_file chunk by chunk as the
+// frames arrive (two chunks of frames on the device, one on the host, whatever the video's length);
+// result() stays empty, saveResult() only logs, and a failure removes the partial file.
 class VideoDecoder : public VideoProcessor {
 public:
     VideoDecoder(const std::string& source_file, const std::string& dest_file, const bool& motioncomp,
-                 int block_size = 0);
+                 int block_size = 0, bool stream_to_file = false);
     bool process() override;
-    void saveResult() const override { VideoProcessor::saveResult(false); }
+    void saveResult() const override;
 
 private:
+    bool processToFile();
     int n_;
+    bool stream_to_file_;
 };
 
 }  // namespace dc
@@ -405,6 +413,17 @@ int64_t ieh_decode_images(ie_ctx* ctx, const uint8_t* enc, size_t enc_pitch, con
 // below the frames' size returns IE_ECAP after the header, as ieh_decode_image.
 int64_t ieh_decode_video(ie_ctx* ctx, const uint8_t* enc, size_t len, int n, uint8_t* out, size_t cap, int* w,
                          int* h, int* frames);
+// The same file decoded chunk by chunk (ie_vdec over the payload; ie_hip.h): open runs the Huffman
+// pass, reads the header (returned through w .. merange) and ie_set_quant, and opens the decoder
+// (chunk_frames as ie_vdec_open; enc may be freed when it returns); next writes whole frames in the
+// file's layout -- Y, then w*h/2 bytes of 0x80 -- into out (host memory), as many as cap holds and
+// the video has left (*got; 0 at the end); the frames in order are ieh_decode_video's bytes.  A
+// truncated file: the frames before the cut, then IE_EFORMAT (ie_vdec_next's contract).
+typedef struct ieh_vdec ieh_vdec;
+int ieh_vdec_open(ie_ctx* ctx, const uint8_t* enc, size_t len, int n, int motioncomp, int chunk_frames, int* w, int* h,
+                  int* frames, int* gop, int* merange, ieh_vdec** out);
+int ieh_vdec_next(ieh_vdec* v, uint8_t* out, size_t cap, int* got);
+int ieh_vdec_close(ieh_vdec* v);
 // Huffman post-pass entirely between device buffers (in, out device memory; out needs
 // ~n + 4 KiB).  Returns output bytes; only the 256-entry histogram and code table cross PCIe.
 int64_t ieh_huffman_encode_device(ie_ctx* ctx, const uint8_t* din, size_t n, uint8_t* dout, size_t cap);
