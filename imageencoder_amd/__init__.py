@@ -94,6 +94,10 @@ def load_library(path: str | None = None) -> C.CDLL:
         L.ie_probe_rd.restype = C.c_int
         L.ie_probe_rd.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, u16p, C.c_int,
                                   u64p, u64p]
+    if hasattr(L, "ie_probe_gop"):  # (absent from an older IE_LIB build under comparison)
+        L.ie_probe_gop.restype = C.c_int
+        L.ie_probe_gop.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   u16p, C.c_int, u64p]
     for name in ("ie_huffman_hist", "ie_huffman_pack", "ie_bitcopy", "ie_decode_frames"):
         if hasattr(L, name):
             getattr(L, name).restype = C.c_int
@@ -185,6 +189,10 @@ def load_host_library(path: str | None = None) -> C.CDLL:
         H.ieh_encode_image_quality.restype = C.c_int64
         H.ieh_encode_image_quality.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                                C.c_uint64, vp, C.c_size_t, ip, C.POINTER(C.c_uint64)]
+    if hasattr(H, "ieh_encode_video_budget"):  # (absent from an older IE_LIB build under comparison)
+        H.ieh_encode_video_budget.restype = C.c_int64
+        H.ieh_encode_video_budget.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, ip]
     H.ieh_encode_video.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, vp, C.c_size_t]
     H.ieh_encode_video_gop.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
@@ -602,6 +610,31 @@ class Codec:
                                         nq, bits.ctypes.data_as(u64p)))
         return bits
 
+    def probe_gop(self, y, w: int, h: int, qs, gop: int, merange: int, nframes: int = 1, rle: bool = True,
+                  stride: int | None = None, frame_pitch: int | None = None, out=None) -> np.ndarray:
+        """:meth:`probe_sizes` for a video with P-frames (ie_probe_gop): shape ``(nq, nframes)``
+        uint64, entry ``[m, f]`` = the ``frame_bits[f]`` of :meth:`encode_gop` with the same ``gop``
+        and ``merange`` after ``set_quant(qs[m])``.  The codec's own matrix is left as it was.
+        ``out``: an optional device tensor of ``nq * nframes`` 64-bit entries, which receives the
+        sums instead -- the call is then asynchronous and returns ``out``."""
+        stride = w if stride is None else stride
+        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        nn = (self.n or 0) ** 2
+        qs = np.ascontiguousarray(np.asarray(qs, dtype=np.uint16).reshape(-1, nn) if nn else
+                                  np.asarray(qs, dtype=np.uint16))
+        nq = qs.shape[0] if nn else 1
+        u64p = C.POINTER(C.c_uint64)
+        if out is not None:
+            if _nbytes(out) < 8 * nq * nframes:
+                raise IEError(IE_EINVAL, "probe_gop: out holds fewer than nq * nframes 64-bit entries")
+            self._chk(self.L.ie_probe_gop(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, gop, merange, int(rle),
+                                          qs.ctypes.data, nq, C.cast(C.c_void_p(_ptr(out)), u64p)))
+            return out
+        bits = np.zeros((max(nq, 1), nframes), dtype=np.uint64)
+        self._chk(self.L.ie_probe_gop(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, gop, merange, int(rle),
+                                      qs.ctypes.data, nq, bits.ctypes.data_as(u64p)))
+        return bits
+
     def probe_rd(self, y, w: int, h: int, qs, nframes: int = 1, rle: bool = True, stride: int | None = None,
                  frame_pitch: int | None = None, out=None):
         """:meth:`probe_sizes`, and the distortion with it (ie_probe_rd): ``(bits, sse)``, each of
@@ -799,6 +832,28 @@ class Codec:
             raise e
         self.n = n
         return out[: int(r)].tobytes(), int(pc.value), int(se.value)
+
+    def encode_video_budget(self, yuv, w: int, h: int, q, n: int, budget: int, gop: int = 1, merange: int = 0,
+                            rle: bool = True, huffman: bool = True, mode: int = MODE_FAST):
+        """A video file (as :meth:`encode_video_file` writes it) with the finest probed scale of
+        ``q`` whose size -- header + the frames' payload, before the Huffman pass -- fits ``budget``
+        bytes (ieh_encode_video_budget, sized by :meth:`probe_gop`): ``(bytes, percent)``.  Raises
+        ``IEError(IE_ECAP, ...)`` (``e.percent`` = 5382) when no scale fits.  The codec's matrix
+        afterwards is the chosen one."""
+        H = load_host_library()
+        q = np.ascontiguousarray(np.asarray(q, dtype=np.uint16).ravel())
+        frames = _nbytes(yuv) // (w * h + w * h // 2)
+        cap = stream_bound(w, h, n, max(frames, 1), 2048) + (w // 16) * (h // 16) * 4 * max(frames, 1) + 64
+        out = np.zeros(cap, dtype=np.uint8)
+        pc = C.c_int(0)
+        r = H.ieh_encode_video_budget(self.h, _ptr(yuv), _nbytes(yuv), w, h, q.ctypes.data, n, int(rle), int(huffman),
+                                      gop, merange, mode, int(budget), out.ctypes.data, cap, C.byref(pc))
+        if r < 0:
+            e = IEError(int(r), self.L.ie_last_error(self.h).decode())
+            e.percent = int(pc.value)
+            raise e
+        self.n = n
+        return out[: int(r)].tobytes(), int(pc.value)
 
     def encode_video_file(self, yuv, w: int, h: int, q, n: int, rle: bool = True, huffman: bool = True,
                           merange: int = 0, mode: int = MODE_FAST, gop: int = 1) -> bytes:

@@ -12,6 +12,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <utility>
 
 #include "host_internal.hpp"
@@ -692,7 +693,8 @@ const int kBudgetLadder[32] = {25,  30,  35,  42,  50,  59,  71,   84,   100,  1
 
 // File bytes (before any Huffman pass) of every percent in `pc` for one frame, and with `sse` the
 // squared error of the decoded frame: one ie_probe_sizes / ie_probe_rd call over the distinct
-// scaled matrices, mapped back to the percents.
+// scaled matrices, mapped back to the percents.  A video file (p.video; sizes only): one
+// ie_probe_gop call over its frames' Y planes, the frames' bits summed.
 int probe_percents(ie_ctx* c, const uint8_t* y, dc::FileParams p, const uint16_t* base, const std::vector<int>& pc,
                    std::vector<uint64_t>& bytes, std::vector<uint64_t>* sse = nullptr) {
     const int nn = p.n * p.n;
@@ -709,8 +711,18 @@ int probe_percents(ie_ctx* c, const uint8_t* y, dc::FileParams p, const uint16_t
     }
     const int nq = int(qs.size() / size_t(nn));
     std::vector<uint64_t> bits(static_cast<size_t>(nq), 0), se(static_cast<size_t>(nq), 0);
-    const int r = sse ? ie_probe_rd(c, y, p.w, p.h, size_t(p.w), 0, 1, p.rle ? 1 : 0, qs.data(), nq, bits.data(), se.data())
-                      : ie_probe_sizes(c, y, p.w, p.h, size_t(p.w), 0, 1, p.rle ? 1 : 0, qs.data(), nq, bits.data());
+    int r;
+    if (p.video) {
+        std::vector<uint64_t> fbits(static_cast<size_t>(nq) * size_t(p.frames), 0);
+        r = ie_probe_gop(c, y, p.w, p.h, size_t(p.w), p.frame_pitch, p.frames, p.gop, p.merange, p.rle ? 1 : 0, qs.data(),
+                         nq, fbits.data());
+        for (int m = 0; m < nq; m++)
+            bits[size_t(m)] = std::accumulate(fbits.begin() + size_t(m) * p.frames, fbits.begin() + size_t(m + 1) * p.frames,
+                                              uint64_t(0));
+    } else {
+        r = sse ? ie_probe_rd(c, y, p.w, p.h, size_t(p.w), 0, 1, p.rle ? 1 : 0, qs.data(), nq, bits.data(), se.data())
+                : ie_probe_sizes(c, y, p.w, p.h, size_t(p.w), 0, 1, p.rle ? 1 : 0, qs.data(), nq, bits.data());
+    }
     if (r) return r;
     bytes.resize(pc.size());
     if (sse) sse->resize(pc.size());
@@ -735,18 +747,20 @@ std::vector<int> refine_percents(int p0, int p1) {
     return fine;
 }
 
-// A host frame goes to the device once, for the probes and the encode.
-int frame_on_device(ie_ctx* c, const uint8_t* y, int w, int h, const uint8_t** dy) {
+// Host frames (px bytes) go to the device once, for the probes and the encode.
+int frames_on_device(ie_ctx* c, const uint8_t* y, size_t px, const uint8_t** dy) {
     *dy = y;
-    if (!dc::is_device(c, y) && w > 0 && h > 0) {
+    if (!dc::is_device(c, y) && px > 0) {
         dc::Scratch& s = dc::scratch(c);
-        const size_t px = size_t(w) * size_t(h);
         int r;
         if ((r = s.pix.reserve(px))) return r;
         if ((r = ie_memcpy(c, s.pix.p, y, px))) return r;
         *dy = s.pix.p;
     }
     return IE_OK;
+}
+int frame_on_device(ie_ctx* c, const uint8_t* y, int w, int h, const uint8_t** dy) {
+    return frames_on_device(c, y, w > 0 && h > 0 ? size_t(w) * size_t(h) : 0, dy);
 }
 
 // The file under `base` scaled to `percent`, which the probe sized at probed_bytes before the Huffman pass.
@@ -772,6 +786,40 @@ int64_t encode_scaled(ie_ctx* c, const uint8_t* dy, dc::FileParams p, const uint
     }
     std::memcpy(out, v.data(), v.size());
     return int64_t(v.size());
+}
+
+// The budget search over device frames dy (an image, or a video's YUV420 frames: p.video): the
+// ladder, the refinement between its two entries, the encode of the smallest percent that fits.
+int64_t encode_budget(ie_ctx* c, const uint8_t* dy, const dc::FileParams& p, const uint16_t* base, size_t budget_bytes,
+                      uint8_t* out, size_t cap, int* percent) {
+    int r;
+    std::vector<int> ladder(kBudgetLadder, kBudgetLadder + 32);
+    std::vector<uint64_t> size;
+    if ((r = probe_percents(c, dy, p, base, ladder, size))) return r;
+    int i1 = -1;  // the smallest ladder percent whose file fits
+    for (int i = 0; i < 32 && i1 < 0; i++)
+        if (size[size_t(i)] <= budget_bytes) i1 = i;
+    if (i1 < 0) {
+        *percent = kBudgetLadder[31];
+        ie_set_error(c, "no scale up to 5382 % meets the budget");
+        return IE_ECAP;
+    }
+    int best = kBudgetLadder[i1];
+    uint64_t best_bytes = size[size_t(i1)];
+    if (i1 > 0) {  // the integers between the two ladder entries, at most 32 of them
+        const std::vector<int> fine = refine_percents(kBudgetLadder[i1 - 1], kBudgetLadder[i1]);
+        if (!fine.empty()) {
+            std::vector<uint64_t> fsize;
+            if ((r = probe_percents(c, dy, p, base, fine, fsize))) return r;
+            for (size_t i = 0; i < fine.size(); i++)
+                if (fsize[i] <= budget_bytes) {
+                    best = fine[i];
+                    best_bytes = fsize[i];
+                    break;
+                }
+        }
+    }
+    return encode_scaled(c, dy, p, base, best, best_bytes, "budget", out, cap, percent);
 }
 }  // namespace
 
@@ -803,33 +851,7 @@ int64_t ieh_encode_image_budget(ie_ctx* c, const uint8_t* y, int w, int h, const
     p.mode = mode;
     const uint8_t* dy;
     if ((r = frame_on_device(c, y, w, h, &dy))) return r;
-    std::vector<int> ladder(kBudgetLadder, kBudgetLadder + 32);
-    std::vector<uint64_t> size;
-    if ((r = probe_percents(c, dy, p, base, ladder, size))) return r;
-    int i1 = -1;  // the smallest ladder percent whose file fits
-    for (int i = 0; i < 32 && i1 < 0; i++)
-        if (size[size_t(i)] <= budget_bytes) i1 = i;
-    if (i1 < 0) {
-        *percent = kBudgetLadder[31];
-        ie_set_error(c, "no scale up to 5382 % meets the budget");
-        return IE_ECAP;
-    }
-    int best = kBudgetLadder[i1];
-    uint64_t best_bytes = size[size_t(i1)];
-    if (i1 > 0) {  // the integers between the two ladder entries, at most 32 of them
-        const std::vector<int> fine = refine_percents(kBudgetLadder[i1 - 1], kBudgetLadder[i1]);
-        if (!fine.empty()) {
-            std::vector<uint64_t> fsize;
-            if ((r = probe_percents(c, dy, p, base, fine, fsize))) return r;
-            for (size_t i = 0; i < fine.size(); i++)
-                if (fsize[i] <= budget_bytes) {
-                    best = fine[i];
-                    best_bytes = fsize[i];
-                    break;
-                }
-        }
-    }
-    return encode_scaled(c, dy, p, base, best, best_bytes, "budget", out, cap, percent);
+    return encode_budget(c, dy, p, base, budget_bytes, out, cap, percent);
 }
 
 int64_t ieh_encode_image_quality(ie_ctx* c, const uint8_t* y, int w, int h, const uint16_t* base, int n, int rle,
@@ -906,6 +928,30 @@ int64_t ieh_encode_video_gop(ie_ctx* c, const uint8_t* yuv, size_t len, int w, i
     if (v.size() > cap) return IE_ECAP;
     std::memcpy(out, v.data(), v.size());
     return int64_t(v.size());
+}
+
+int64_t ieh_encode_video_budget(ie_ctx* c, const uint8_t* yuv, size_t len, int w, int h, const uint16_t* base, int n,
+                                int rle, int huffman, int gop, int merange, int mode, size_t budget_bytes, uint8_t* out,
+                                size_t cap, int* percent) {
+    if (!c || !yuv || !base || !out || !percent || (n != 4 && n != 8) || w <= 0 || h <= 0) return IE_EINVAL;
+    dc::FileParams p;
+    p.w = w;
+    p.h = h;
+    p.n = n;
+    p.rle = rle != 0;
+    p.huffman = huffman != 0;
+    p.mode = mode;
+    p.video = true;
+    p.frame_pitch = size_t(w) * h + size_t(w) * h / 2;
+    p.frames = int(len / p.frame_pitch);
+    p.gop = gop < 1 ? 1 : gop;
+    p.merange = merange;
+    if (p.frames <= 0 || p.frames > 32767) return IE_EINVAL;
+    int r;
+    if ((r = ie_set_quant(c, base, n))) return r;  // the probe's block size and transform tables
+    const uint8_t* dy;
+    if ((r = frames_on_device(c, yuv, size_t(p.frames) * p.frame_pitch, &dy))) return r;
+    return encode_budget(c, dy, p, base, budget_bytes, out, cap, percent);
 }
 
 int64_t ieh_decode_image(ie_ctx* c, const uint8_t* enc, size_t len, int n, uint8_t* out, size_t cap, int* w, int* h) {

@@ -14,19 +14,51 @@ const uint8_t kZz8[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11
                           41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                           30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
+}  // namespace
+
+namespace iec {
+
+int check_candidates(ie_ctx* c, const uint16_t* q, int nq) {
+    if (nq < 1 || nq > IE_PROBE_MAX)
+        return fail(c, IE_EINVAL, "nq must be in [1, " + std::to_string(int(IE_PROBE_MAX)) + "]");
+    const int nn = c->n * c->n;
+    for (int m = 0; m < nq; m++)
+        for (int k = 0; k < nn; k++)
+            if (q[size_t(m) * nn + k] == 0)
+                return fail(c, IE_EINVAL, "candidate matrix " + std::to_string(m) + " has a zero entry (entries must be > 0)");
+    return IE_OK;
+}
+
+// (an earlier call's copy out of the pinned block may still be in flight when the calls are
+// asynchronous: the event after it is waited for before the block is written again)
+int stage_candidates(ie_ctx* c, const uint16_t* q, int nq) {
+    const int n = c->n, nn = n * n;
+    const size_t qcap = size_t(IE_PROBE_MAX) * 64;
+    int r;
+    if ((r = c->h_probe_q.reserve(c, qcap))) return r;
+    if ((r = c->d_probe_q.reserve(c, qcap))) return r;
+    if ((r = c->ev_probe.create(c, hipEventDisableTiming))) return r;
+    if (c->probe_recorded) HIPCHK(c, hipEventSynchronize(c->ev_probe));
+    const uint8_t* zz = n == 4 ? kZz4 : kZz8;
+    for (int m = 0; m < nq; m++)
+        for (int z = 0; z < nn; z++) c->h_probe_q[size_t(m) * nn + z] = q[size_t(m) * nn + zz[z]];
+    HIPCHK(c, hipMemcpyAsync(c->d_probe_q, c->h_probe_q, size_t(nq) * nn * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_probe, c->stream));
+    c->probe_recorded = true;
+    return IE_OK;
+}
+
+}  // namespace iec
+
+namespace {
 // Both entry points.  sse == nullptr: ie_probe_sizes (bits required); else ie_probe_rd (bits optional).
 int probe(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes, int use_rle,
           const uint16_t* q, int nq, uint64_t* bits, uint64_t* sse, bool rd) {
     if (!c || !y || !q || (rd ? !sse : !bits)) return IE_EINVAL;
     int r = check_frames(c, w, h, nframes, stride, frame_pitch);
     if (r) return r;
-    if (nq < 1 || nq > IE_PROBE_MAX)
-        return fail(c, IE_EINVAL, "nq must be in [1, " + std::to_string(int(IE_PROBE_MAX)) + "]");
-    const int n = c->n, nn = n * n;
-    for (int m = 0; m < nq; m++)
-        for (int k = 0; k < nn; k++)
-            if (q[size_t(m) * nn + k] == 0)
-                return fail(c, IE_EINVAL, "candidate matrix " + std::to_string(m) + " has a zero entry (entries must be > 0)");
+    if ((r = check_candidates(c, q, nq))) return r;
+    const int n = c->n;
     HIPCHK(c, hipSetDevice(c->device));
     const bool in_dev = is_device_ptr(y);
     const bool res_dev = is_device_ptr(rd ? sse : bits);
@@ -38,19 +70,7 @@ int probe(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame
     const uint8_t* dy;
     if ((r = stage_in(c, y, in_dev, frames_span(nframes, frame_pitch, stride, w, h), &dy))) return r;
 
-    // the candidates, zig-zag ordered, through pinned memory (an earlier call's copy out of it may
-    // still be in flight when the calls are asynchronous)
-    const size_t qcap = size_t(IE_PROBE_MAX) * 64;
-    if ((r = c->h_probe_q.reserve(c, qcap))) return r;
-    if ((r = c->d_probe_q.reserve(c, qcap))) return r;
-    if ((r = c->ev_probe.create(c, hipEventDisableTiming))) return r;
-    if (c->probe_recorded) HIPCHK(c, hipEventSynchronize(c->ev_probe));
-    const uint8_t* zz = n == 4 ? kZz4 : kZz8;
-    for (int m = 0; m < nq; m++)
-        for (int z = 0; z < nn; z++) c->h_probe_q[size_t(m) * nn + z] = q[size_t(m) * nn + zz[z]];
-    HIPCHK(c, hipMemcpyAsync(c->d_probe_q, c->h_probe_q, size_t(nq) * nn * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_probe, c->stream));
-    c->probe_recorded = true;
+    if ((r = stage_candidates(c, q, nq))) return r;
 
     // host results: the sums (ie_probe_rd: the bits, then the squared errors) in one device block
     const size_t nsums = size_t(nq) * size_t(nframes);

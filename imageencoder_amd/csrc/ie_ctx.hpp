@@ -244,6 +244,8 @@ struct ie_ctx {
     bool probe_recorded = false;
     iec::Buf<uint64_t> d_probe_bits;
     iec::Buf<uint64_t, iec::Mem::Pinned> h_probe_out;
+    // ie_probe_gop: two reconstructed frames per (group, candidate) pair of one wave
+    iec::Buf<uint8_t> d_probe_gop;
 };
 
 namespace iec {
@@ -421,6 +423,12 @@ int gop_wave_scratch(ie_ctx* c, int w, int h, int gop, int merange, size_t Gw, G
 int launch_gop_wave(ie_ctx* c, const GopWave& W, const uint8_t* wy, int w, int h, size_t stride, size_t frame_pitch,
                     int gw, int nfw, int merange, int use_rle, int mode, uint32_t* dout, uint64_t start_bit,
                     const uint64_t* base_dev, uint64_t* fpos);
+
+// ---- ie_capi_probe.cpp: the candidates of a probe (ie_probe_sizes, ie_probe_rd, ie_probe_gop)
+// nq in [1, IE_PROBE_MAX] and no zero entry, else IE_EINVAL (the message names the matrix)
+int check_candidates(ie_ctx* c, const uint16_t* q, int nq);
+// The candidates in zig-zag order to d_probe_q on the stream, through pinned memory.
+int stage_candidates(ie_ctx* c, const uint16_t* q, int nq);
 
 // ---- ie_capi_decode.cpp: the record parse's chunk plan and scratch (ie_capi_vdec.cpp plans its
 // chunks of frames with them)

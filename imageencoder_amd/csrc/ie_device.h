@@ -373,6 +373,33 @@ void launch_pframe(const PfArgs& a, int n, uint64_t* tile_scratch, hipStream_t s
 // no look-back chain per group.  groups <= 65535 (grid.y).
 void launch_pframe_groups(const PfArgs& a, int n, int groups, uint64_t* tile_scratch, hipStream_t s);
 
+// ie_probe_gop (ie_pframe.hip): one P-frame step of `groups` groups of pictures under nm candidate
+// matrices, sizes only.  blockIdx.y = the group, blockIdx.z = a range of mper candidates.
+struct PgArgs {
+    const uint8_t* cur;      // group 0's frame of this step, rows cs apart; group g's: + g * g_cur
+    uint64_t cs, g_cur;
+    // Candidate m of group g predicts from ref + g * g_ref + m * m_ref, rows rs apart.  m_ref == 0:
+    // one reference for all candidates (a group's first P-frame: the I-frame's source) -- search
+    // and unquantised coefficients are then formed once per macroblock.
+    const uint8_t* ref;
+    uint64_t rs, g_ref, m_ref;
+    // its reconstruction: rec + g * g_rec + m * m_rec, [h][w]; nullptr: not stored (no later step reads it)
+    uint8_t* rec;
+    uint64_t g_rec, m_rec;
+    int w, h, mbx, mby;
+    int rle, merange, mv_bits;
+    const EncTables* tab;    // P, R and S (they do not depend on the matrix)
+    const uint16_t* q;       // [nm][16] the candidates in ZIG-ZAG order (device)
+    int nm, mper;            // candidates of the launch (m = 0 .. nm-1), candidates per wave (1 .. 64)
+    // 2 * mv_bits + the record bits of every macroblock are added to bits[m * m_bits + g * g_bits]
+    unsigned long long* bits;
+    uint64_t m_bits, g_bits;
+};
+void launch_pframe_probe(const PgArgs& a, int groups, hipStream_t s);
+// dst[m * nframes + g * gop] = src[m * groups + g] (the I-frames' sums); fill: every other entry = pconst
+void launch_pframe_probe_scatter(const unsigned long long* src, unsigned long long* dst, int nq, int nframes, int gop,
+                                 int groups, int fill, unsigned long long pconst, hipStream_t s);
+
 // Splice of a video's groups of pictures (ie_encode_gop_groups): group g's private slot (bits
 // [0, len_g) from slots + g * slot_words) goes to out at bit base + sum_{k<g} len_k.
 struct GopSplice {

@@ -17,6 +17,8 @@
 // placed by a two-level scan of their lengths and ORed into the zeroed stream.  The same kernels
 // run one frame of many groups of pictures at once (blockIdx.y = the group, each with a stream slot
 // of its own); gop_splice_kernel then moves the slots' payloads end to end (ie_encode_gop_groups).
+// pf_probe_kernel is the macroblock pass under many candidate matrices with nothing emitted: the
+// P-frame sizes of ie_probe_gop.
 #include <hip/hip_runtime.h>
 
 #include "ie_common.hpp"
@@ -522,7 +524,199 @@ __global__ __launch_bounds__(kMbTPB) void pf_mvcopy_kernel(const uint8_t* in, ui
     for (int j = 0; j < 4; j++) dp[j] = sp[j];
 }
 
+// ---- ie_probe_gop: the size pass of pf_macroblock_kernel<4> under many candidate matrices.
+//
+// The same steps per macroblock and candidate -- search, prediction error, forward transform,
+// round((acc * S) / q), size4 / rec_len, inverse, expandDifferences -- with nothing emitted: no
+// coefficient or record-length array, no scan, no stream.  The wave adds 2 * mv_bits + the record
+// lengths of its macroblock to the candidate's sum of the frame.
+//
+// blockIdx.y = the group of pictures, blockIdx.z = a range of a.mper candidates, looped over inside
+// the wave.  Candidate m predicts from a.ref + m * a.m_ref and leaves its reconstruction in a.rec +
+// m * a.m_rec.  At a group's first P-frame the reference is the I-frame's source (m_ref == 0):
+// search, prediction error and the unquantised coefficients acc * S do not depend on the
+// candidate and are formed once, in the operation order of the encode kernel -- the quotient
+// (acc * S) / q rounds the same product, so sharing it changes no bit.  From the second P-frame on
+// every candidate has a reference of its own and the whole macroblock is redone per candidate.
+
+// the search of pf_macroblock_kernel (Block.cpp:272-329), statement for statement
+struct PfVec {
+    int cx, cy;    // the motion vector
+    int bbx, bby;  // the best block, absolute (the first one is the block at (0, 0))
+};
+__device__ __forceinline__ PfVec pf_search(uint32_t c4, const uint8_t* ref, uint64_t rs, int merange, int mx, int my,
+                                           int py, int px, int W16, int H16) {
+    int cx = 0, cy = 0, r = merange / 2;
+    int bbx = 0, bby = 0;
+    uint32_t best = 0xFFFFFFFFu;
+    while (r != 0) {
+        uint32_t d[9];
+        int qx[9], qy[9];
+#pragma unroll
+        for (int p = 0; p < 9; p++) {
+            qx[p] = clamp16(cx + kSx[p] * r + mx, W16);
+            qy[p] = clamp16(cy + kSy[p] * r + my, H16);
+            d[p] = __builtin_amdgcn_sad_u8(c4, load4(ref + size_t(qy[p] + py) * rs + qx[p] + px), 0u);
+        }
+#pragma unroll
+        for (int p = 0; p < 9; p++) d[p] = wave_sum(d[p]);
+        int np = -1, nbx = 0, nby = 0;
+        uint32_t nd = best;
+#pragma unroll
+        for (int p = 0; p < 9; p++) {
+            if (p > 0 && qx[p] == mx && qy[p] == my) continue;  // Block.cpp:297-301
+            if (d[p] <= nd) {
+                np = p;
+                nd = d[p];
+                nbx = qx[p];
+                nby = qy[p];
+            }
+        }
+        if (np < 0) break;
+        cx += kSx[np] * r;
+        cy += kSy[np] * r;
+        r /= 2;
+        best = nd;
+        bbx = nbx;
+        bby = nby;
+    }
+    return PfVec{cx, cy, bbx, bby};
+}
+
+__global__ __launch_bounds__(kMbTPB) void pf_probe_kernel(PgArgs a) {
+    __shared__ double xs[256];
+    __shared__ double Ps[256], Rs[256], Ss[16];
+    __shared__ int16_t cq[256];
+    extern __shared__ __attribute__((aligned(16))) double pg_q[];  // [candidates of this wave][16], natural order
+    const int l = threadIdx.x;
+    const int mb = blockIdx.x;
+    const int m0 = int(blockIdx.z) * a.mper;          // the wave's candidates: [m0, m0 + cnt) of the launch
+    const int cnt = min(a.mper, a.nm - m0);           // (1 .. 64)
+    const uint64_t g = blockIdx.y;
+    const uint8_t* cur = a.cur + g * a.g_cur;
+    const uint8_t* ref0 = a.ref + g * a.g_ref + uint64_t(m0) * a.m_ref;
+    uint8_t* rec0 = a.rec ? a.rec + g * a.g_rec + uint64_t(m0) * a.m_rec : nullptr;
+    if (mb >= a.mbx * a.mby) {  // the uncovered strips (pf_strip_pixel), into every candidate's buffer
+        const size_t i = size_t(mb - a.mbx * a.mby) * kMbTPB + size_t(l);
+        const int hc = a.mby * kMB, wc = a.mbx * kMB;
+        const size_t nbot = size_t(a.h - hc) * a.w, nright = size_t(hc) * (a.w - wc);
+        if (!rec0 || i >= nbot + nright) return;
+        int x, y;
+        if (i < nbot) {
+            y = hc + int(i / size_t(a.w));
+            x = int(i % size_t(a.w));
+        } else {
+            const size_t j = i - nbot;
+            const int rw = a.w - wc;
+            y = int(j / size_t(rw));
+            x = wc + int(j % size_t(rw));
+        }
+        const uint8_t v = uint8_t(min(2 * int(cur[size_t(y) * a.cs + x]), 255));
+        for (int i2 = 0; i2 < cnt; i2++) rec0[uint64_t(i2) * a.m_rec + size_t(y) * a.w + x] = v;
+        return;
+    }
+    const int mx = (mb % a.mbx) * kMB, my = (mb / a.mbx) * kMB;
+    const int py = l >> 2, px = (l & 3) * 4;
+    const int W16 = a.w - kMB, H16 = a.h - kMB;
+    const uint32_t c4 = load4(cur + size_t(my + py) * a.cs + mx + px);
+    for (int i = l; i < 256; i += kMbTPB) {
+        Ps[i] = a.tab->P[i];
+        Rs[i] = a.tab->R[i];
+    }
+    if (l < 16) Ss[l] = a.tab->S[l];
+    for (int i = l; i < cnt * 16; i += kMbTPB)  // a.q is in zig-zag order (ie_probe_sizes' array)
+        pg_q[(i & ~15) + kZz4[i & 15]] = double(a.q[size_t(m0) * 16 + i]);
+    const bool shared = a.m_ref == 0;
+    const int m = l >> 2, gq = (l & 3) * 4;  // forward: microblock l/4, coefficients 4(l%4)..+3
+    const int mi = (py >> 2) * 4 + (l & 3);  // prediction error: the lane's row of microblock mi
+    PfVec v{0, 0, 0, 0};
+    double D[4] = {0.0, 0.0, 0.0, 0.0};      // acc * S of the lane's coefficients
+    uint32_t mine = 0;                       // lane i: the macroblock's bits under candidate m0 + i
+    for (int i = 0; i < cnt; i++) {
+        const uint8_t* ref = ref0 + uint64_t(i) * a.m_ref;
+        if (i == 0 || !shared) {
+            v = pf_search(c4, ref, a.rs, a.merange, mx, my, py, px, W16, H16);
+            const uint32_t r4 = load4(ref + size_t(v.bby + py) * a.rs + v.bbx + px);
+            __syncthreads();  // (the previous candidate's reads of cq and the tables' staging)
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                xs[mi * 16 + (py & 3) * 4 + j] =
+                    (double(int((c4 >> (8 * j)) & 255u)) - double(int((r4 >> (8 * j)) & 255u))) + double(-128);
+            __syncthreads();
+            const double* x = xs + m * 16;
+            double acc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const double xk = x[k];
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc[j] = acc[j] + Ps[(gq + j) * 16 + k] * xk;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) D[j] = acc[j] * Ss[gq + j];
+        } else {
+            __syncthreads();  // the previous candidate's reads of cq
+        }
+        const double* qs = pg_q + i * 16;
+#pragma unroll
+        for (int j = 0; j < 4; j++) cq[m * 16 + gq + j] = int16_t(round(D[j] / qs[gq + j]));
+        __syncthreads();
+        const uint32_t len = gq == 0 ? rec_len(size4(cq + m * 16, a.rle), a.rle) : 0u;
+        const uint32_t sum = wave_sum(len) + 2u * uint32_t(a.mv_bits);
+        if (l == i) mine = sum;
+        if (!rec0) continue;  // (wave-uniform) the group's last P-frame: nothing reads its reconstruction
+        // ---- inverse + expandDifferences, as the encode kernel: lane = (microblock l/4, pixel row l%4)
+        double tt[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int uv = 0; uv < 16; uv++) {
+            const double yv = double(cq[m * 16 + uv]) * qs[uv];
+#pragma unroll
+            for (int j = 0; j < 4; j++) tt[j] = tt[j] + Rs[uv * 16 + gq + j] * yv;
+        }
+        const int ccx = clamp16(mx + v.cx, W16), ccy = clamp16(my + v.cy, H16);
+        const int ppy = (m >> 2) * 4 + (l & 3), ppx = (m & 3) * 4;
+        const uint32_t b4 = load4(ref + size_t(ccy + ppy) * a.rs + ccx + ppx);
+        uint32_t o4 = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const double vv = double(int((b4 >> (8 * j)) & 255u)) + (tt[j] + double(128));
+            o4 |= uint32_t(uint8_t(vv < 0.0 ? 0.0 : (vv > 255.0 ? 255.0 : vv))) << (8 * j);
+        }
+        *reinterpret_cast<uint32_t*>(rec0 + uint64_t(i) * a.m_rec + size_t(my + ppy) * a.w + mx + ppx) = o4;
+    }
+    if (l < cnt) atomicAdd(a.bits + uint64_t(m0 + l) * a.m_bits + g * a.g_bits, (unsigned long long)mine);
+}
+
+// ie_probe_gop: the I-frames' sums (src[m * groups + g], ie_probe_sizes' layout over the I-frames
+// alone) go to their entries of the table, dst[m * nframes + g * gop]; with fill the P-frames' entries
+// are the constant pconst (8x8 blocks code vectors only), else they are left to pf_probe_kernel's sums.
+__global__ __launch_bounds__(kTPB) void pf_probe_scatter_kernel(const unsigned long long* src, unsigned long long* dst,
+                                                                int nq, int nframes, int gop, int groups, int fill,
+                                                                unsigned long long pconst) {
+    const uint64_t i = uint64_t(blockIdx.x) * kTPB + threadIdx.x;
+    if (i >= uint64_t(nq) * uint64_t(nframes)) return;
+    const int m = int(i / uint64_t(nframes)), f = int(i % uint64_t(nframes));
+    if (f % gop == 0) dst[i] = src[uint64_t(m) * groups + f / gop];
+    else if (fill) dst[i] = pconst;
+}
+
 }  // namespace
+
+void launch_pframe_probe(const PgArgs& a, int groups, hipStream_t s) {
+    const int nmb = a.mbx * a.mby;
+    const size_t px = a.rec ? size_t(a.w) * a.h - size_t(nmb) * kMB * kMB : 0;  // the strips only feed a reconstruction
+    const unsigned grid = unsigned(nmb) + unsigned((px + kMbTPB - 1) / kMbTPB);
+    const unsigned gz = unsigned((a.nm + a.mper - 1) / a.mper);
+    if (grid)
+        hipLaunchKernelGGL(pf_probe_kernel, dim3(grid, unsigned(groups), gz), dim3(kMbTPB), size_t(a.mper) * 16 * sizeof(double),
+                           s, a);
+}
+
+void launch_pframe_probe_scatter(const unsigned long long* src, unsigned long long* dst, int nq, int nframes, int gop,
+                                 int groups, int fill, unsigned long long pconst, hipStream_t s) {
+    const uint64_t total = uint64_t(nq) * uint64_t(nframes);
+    hipLaunchKernelGGL(pf_probe_scatter_kernel, dim3(unsigned((total + kTPB - 1) / kTPB)), dim3(kTPB), 0, s, src, dst, nq,
+                       nframes, gop, groups, fill, pconst);
+}
 
 void launch_pframe_mvcopy(const uint8_t* stream, uint64_t start_bit, const uint64_t* dstart, uint64_t nbits, int mv_bits,
                           const uint8_t* ref, uint64_t rs, uint8_t* out, uint64_t os, int w, int h, hipStream_t s) {

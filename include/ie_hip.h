@@ -214,6 +214,31 @@ int ie_probe_sizes(ie_ctx* ctx, const uint8_t* y, int w, int h, size_t stride, s
 int ie_probe_rd(ie_ctx* ctx, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch,
                 int nframes, int use_rle, const uint16_t* q, int nq, uint64_t* bits, uint64_t* sse);
 
+/* ---- Size probe for videos with P-frames: ie_probe_sizes' question for ie_encode_gop.
+ *   y .. nframes, gop, merange, use_rle   as ie_encode_gop (y host or device memory) and its checks
+ *                with its codes, the output capacity apart: dimensions, merange in [0, 32767],
+ *                frames, P-frames with W % 16 != 0 and H >= 32; then ie_probe_sizes' checks of nq
+ *                and of zero matrix entries
+ *   q, nq, bits  as ie_probe_sizes
+ * bits[m*nframes + f] equals the frame_bits[f] that ie_encode_gop (and ie_encode_gop_groups) returns
+ * for these frames after ie_set_quant(ctx, q + m*n*n, n), in either mode.  gop <= 1 or nframes == 1
+ * is ie_probe_sizes.  I-frames (f % gop == 0) are sized by ie_probe_sizes' kernel.  P-frames with 4x4
+ * blocks run the encoder's macroblock steps per candidate -- search, FP64 transform of the
+ * prediction error, round((acc * S) / q), record sizes, inverse, reconstruction -- and emit nothing;
+ * the first P-frame of a group predicts from the I-frame's source pixels, which all candidates
+ * share, so its search and unquantised coefficients are formed once.  The launches are as deep as
+ * gop, not nframes.  P-frames with 8x8 blocks carry vectors only: (w/16)*(h/16)*2*bits(merange).
+ *  - Scratch: two reconstructed frames per (group, candidate) pair, owned by the context.  A call
+ *    that would need more than 1 GiB runs as waves on the stream: whole groups with all candidates
+ *    while they fit, else one group at a time with chunks of candidates.  IE_PROBE_GOP_MAX (read on
+ *    every call) lowers the pairs per wave; it never changes the result.
+ *  - Device `bits`: asynchronous on the context's stream (bits is zeroed there).  Host `bits`: one
+ *    synchronisation and one read-back, however many waves run.
+ *  - The context's matrix, tables, chain state, ie_last_end_bits and the encoders' gop scratch are
+ *    left as they were: an ie_encode_gop after a probe equals the one before it. */
+int ie_probe_gop(ie_ctx* ctx, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,
+                 int gop, int merange, int use_rle, const uint16_t* q, int nq, uint64_t* bits);
+
 /* ---- Device memory on the context's stream (for hosts that keep streams device-resident
  * between stages, e.g. the host library's encode -> Huffman pipeline).  ie_memcpy infers the
  * direction of each pointer and is asynchronous only when both are device memory. */

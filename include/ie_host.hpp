@@ -388,6 +388,15 @@ int64_t ieh_encode_video(ie_ctx* ctx, const uint8_t* yuv, size_t len, int w, int
 // P-frames' motion search + coded error through ie_encode_gop_groups).  gop = 1: ieh_encode_video.
 int64_t ieh_encode_video_gop(ie_ctx* ctx, const uint8_t* yuv, size_t len, int w, int h, const uint16_t* q, int n,
                              int rle, int huffman, int gop, int merange, int mode, uint8_t* out, size_t cap);
+// Whole video file (exactly as ieh_encode_video_gop writes it) with the FINEST probed scale of `base`
+// whose file fits budget_bytes: ieh_encode_image_budget's contract, search, error codes and messages
+// for a video.  The size judged is ceil((video header bits for the scaled matrix + the bits of all
+// frames) / 8) before any Huffman pass, the frames' bits from ie_probe_gop (one call over the
+// ladder's distinct matrices, one over the refinement).  The frames lie 1.5 w h bytes apart and
+// only Y is read; host frames go to the device once, for the probes and the encode.
+int64_t ieh_encode_video_budget(ie_ctx* ctx, const uint8_t* yuv, size_t len, int w, int h, const uint16_t* base,
+                                int n, int rle, int huffman, int gop, int merange, int mode, size_t budget_bytes,
+                                uint8_t* out, size_t cap, int* percent);
 // Decode an image file (host buffer) with block size n: pixels into out (w*h bytes).  A cap
 // below w*h returns IE_ECAP with *w / *h set, right after the header (the payload is not decoded):
 // call with cap = 0 to size the buffer.

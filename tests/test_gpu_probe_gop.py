@@ -1,0 +1,225 @@
+"""GPU: ie_probe_gop (Codec.probe_gop) against the CPU oracle.  The truth for candidate m and frame f
+is the frame_bits[f] of oracle.encode_gop under that matrix, one oracle call per candidate; for a few
+candidates the library's own encode_gop / encode_gop_groups after set_quant are compared too.
+
+Shapes are the smallest that reach each way the kernel can go wrong: one macroblock with a ragged
+last group (16 x 16 x 5, gop 3; merange 0 and 1 search nothing), a shared first step followed by two
+steps that chain per-candidate reconstructions (32 x 32 x 4, gop 4), a bottom and a right strip
+(48 x 40, 24 x 16), 48 macroblocks x 2 groups whose atomics meet in one sum (128 x 96 x 6), padded
+rows and frames, waves of groups and chunks of candidates (IE_PROBE_GOP_MAX).  The candidates differ
+for real -- the sweep of tests/matrix_sweep.py plus the base matrix scaled from 25 % to 5382 % -- so a
+mix-up between two candidates' reconstruction buffers changes bits from the second P-frame on."""
+import numpy as np
+import pytest
+
+from imageencoder_amd import IE_EINVAL, IE_ENOQUANT, MODE_EXACT, MODE_FAST, IEError, scale_matrix, synth
+from tests import matrix_sweep as MS
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def codec():
+    from imageencoder_amd import Codec
+    return Codec(0)
+
+
+def _base(n):
+    return MS.by_name(n, "jpeg_like" if n == 4 else "annex_k")
+
+
+def _candidates(n):
+    """The context's own matrix first, the sweep, the base scaled across the budget ladder's range."""
+    qs = [_base(n)] + [q for _, q in MS.sweep(n)] + [scale_matrix(_base(n), p) for p in (25, 59, 336, 1345, 5382)]
+    assert len(qs) <= 64
+    return np.stack(qs)
+
+
+def _few(n):
+    return _candidates(n)[[0, 2, -5, -2, -1]]
+
+
+def _expected(oracle, y, n, qs, gop, merange, rle=True, **layout):
+    return np.stack([oracle.encode_gop(y, n, q, gop, merange, rle=rle, **layout)[2] for q in qs]).astype(np.uint64)
+
+
+def _contents(n, f, h, w):
+    return [("noise", synth.frames("U", w, h, f, seed=31)), ("shift", synth.frames("shiftA", w, h, f, seed=5)),
+            ("flat", synth.frames("flat128", w, h, f)), ("ties", MS.tie_frames(n, _base(n), w, h, f, seed=2))]
+
+
+def _check(got, exp, what):
+    assert got.dtype == np.uint64 and got.shape == exp.shape
+    bad = np.argwhere(got != exp)
+    assert bad.size == 0, (what, "candidate, frame:", bad[:4].tolist(), got[bad[0][0]], exp[bad[0][0]])
+
+
+@pytest.mark.parametrize("rle", [True, False], ids=["rle", "norle"])
+@pytest.mark.parametrize("merange", [0, 1, 16])
+def test_one_macroblock_ragged_last_group(codec, oracle, merange, rle):
+    n, w, h, f, gop = 4, 16, 16, 5, 3
+    qs = _candidates(n)
+    codec.set_quant(_base(n), n)
+    for kind, y in _contents(n, f, h, w):
+        _check(codec.probe_gop(y, w, h, qs, gop, merange, nframes=f, rle=rle),
+               _expected(oracle, y, n, qs, gop, merange, rle), kind)
+
+
+def test_shared_first_step_then_chained_reconstructions(codec, oracle):
+    """32 x 32 x 4, gop 4, every candidate in one call: step 1 shares the reference, steps 2 and 3
+    predict from every candidate's own reconstruction."""
+    n, w, h, f, gop, merange = 4, 32, 32, 4, 4, 16
+    qs = _candidates(n)
+    codec.set_quant(_base(n), n)
+    for kind, y in _contents(n, f, h, w):
+        exp = _expected(oracle, y, n, qs, gop, merange)
+        _check(codec.probe_gop(y, w, h, qs, gop, merange, nframes=f), exp, kind)
+        if kind == "noise":  # the candidates do differ, on the P-frames too
+            assert len({tuple(r[1:]) for r in exp.tolist()}) > len(qs) // 2
+
+
+@pytest.mark.parametrize("w,h", [(48, 40), (24, 16)], ids=["bottom_strip", "right_strip"])
+def test_uncovered_strips(codec, oracle, w, h):
+    n, f, gop, merange = 4, 3, 3, 16
+    qs = _candidates(n)
+    codec.set_quant(_base(n), n)
+    for kind, y in _contents(n, f, h, w)[:2]:
+        _check(codec.probe_gop(y, w, h, qs, gop, merange, nframes=f), _expected(oracle, y, n, qs, gop, merange), kind)
+
+
+def test_many_macroblocks_add_into_one_sum(codec, oracle):
+    import torch
+    n, w, h, f, gop, merange = 4, 128, 96, 6, 3, 16
+    qs = _few(n)
+    codec.set_quant(_base(n), n)
+    for kind, y in _contents(n, f, h, w)[:2]:
+        got = codec.probe_gop(torch.from_numpy(y).cuda(), w, h, qs, gop, merange, nframes=f)
+        _check(got, _expected(oracle, y, n, qs, gop, merange), kind)
+
+
+@pytest.mark.parametrize("w,h", [(48, 40), (32, 32)])
+def test_8x8_pframes_are_a_closed_form(codec, oracle, w, h):
+    n, f, gop, merange = 8, 5, 3, 16
+    qs = _candidates(n)
+    codec.set_quant(_base(n), n)
+    y = synth.frames("U", w, h, f, seed=9)
+    got = codec.probe_gop(y, w, h, qs, gop, merange, nframes=f)
+    _check(got, _expected(oracle, y, n, qs, gop, merange), "noise")
+    pf = [k for k in range(f) if k % gop]
+    assert (got[:, pf] == (w // 16) * (h // 16) * 2 * oracle.bits_needed(merange)).all()
+    assert len(set(got[:, 0].tolist())) > 1 and len(set(got[:, 3].tolist())) > 1  # the I-frames vary
+    codec.set_quant(_base(4), 4)
+
+
+def test_padded_rows_and_frames_host_and_device(codec, oracle):
+    """64 x 48 x 7, gop 3, stride = w + 13, padded frame_pitch; host and device y, host and device
+    bits -- all four give the oracle's table."""
+    import torch
+    n, w, h, f, gop, merange = 4, 64, 48, 7, 3, 16
+    stride, pitch = w + 13, (w + 13) * h + 41
+    qs = _few(n)
+    codec.set_quant(_base(n), n)
+    y = synth.frames("shiftB", w, h, f, seed=3)
+    buf = np.full(f * pitch, 0xA5, dtype=np.uint8)
+    for k in range(f):
+        buf[k * pitch: k * pitch + h * stride].reshape(h, stride)[:, :w] = y[k]
+    exp = _expected(oracle, buf, n, qs, gop, merange, stride=stride, frame_pitch=pitch, dims=(f, h, w))
+    np.testing.assert_array_equal(exp, _expected(oracle, y, n, qs, gop, merange))
+    dbuf = torch.from_numpy(buf).cuda()
+    for src in (buf, dbuf):
+        got = codec.probe_gop(src, w, h, qs, gop, merange, nframes=f, stride=stride, frame_pitch=pitch)
+        _check(got, exp, "host bits")
+        dev = torch.full((len(qs) * f,), -1, dtype=torch.int64, device="cuda")
+        assert codec.probe_gop(src, w, h, qs, gop, merange, nframes=f, stride=stride, frame_pitch=pitch, out=dev) is dev
+        codec.sync()
+        _check(dev.cpu().numpy().view(np.uint64).reshape(len(qs), f), exp, "device bits")
+
+
+def test_waves_never_change_the_table(codec, oracle, monkeypatch):
+    """IE_PROBE_GOP_MAX = 1, 3 (chunks of candidates within one group, a partial last chunk), nq and
+    nq + 1 (waves of one group with all candidates)."""
+    n, w, h, f, gop, merange = 4, 32, 32, 7, 3, 16
+    qs = _few(n)
+    nq = len(qs)
+    codec.set_quant(_base(n), n)
+    y = synth.frames("U", w, h, f, seed=17)
+    monkeypatch.delenv("IE_PROBE_GOP_MAX", raising=False)
+    ref = codec.probe_gop(y, w, h, qs, gop, merange, nframes=f)
+    _check(ref, _expected(oracle, y, n, qs, gop, merange), "unset")
+    for cap in (1, 3, nq, nq + 1):
+        monkeypatch.setenv("IE_PROBE_GOP_MAX", str(cap))
+        _check(codec.probe_gop(y, w, h, qs, gop, merange, nframes=f), ref, f"IE_PROBE_GOP_MAX={cap}")
+
+
+def test_arguments(codec, oracle):
+    n, w, h, f, gop, merange = 4, 32, 32, 4, 2, 8
+    y = synth.frames("U", w, h, f, seed=5)
+    codec.set_quant(_base(n), n)
+    q64 = np.stack([scale_matrix(_base(n), 30 + 7 * k) for k in range(64)])
+    exp = _expected(oracle, y, n, q64, gop, merange)
+    _check(codec.probe_gop(y, w, h, q64, gop, merange, nframes=f), exp, "nq = 64")
+    _check(codec.probe_gop(y, w, h, q64[5:6], gop, merange, nframes=f), exp[5:6], "nq = 1")
+    with pytest.raises(IEError) as e:
+        codec.probe_gop(y, w, h, np.concatenate([q64, q64[:1]]), gop, merange, nframes=f)
+    assert e.value.code == IE_EINVAL
+    bad = q64[:4].copy()
+    bad[2, 9] = 0
+    with pytest.raises(IEError) as e:
+        codec.probe_gop(y, w, h, bad, gop, merange, nframes=f)
+    assert e.value.code == IE_EINVAL and "matrix 2" in str(e.value)
+    with pytest.raises(IEError) as e:  # W % 16 != 0 with H >= 32
+        codec.probe_gop(np.zeros((2, 32, 40), dtype=np.uint8), 40, 32, q64[:1], 2, merange, nframes=2)
+    assert e.value.code == IE_EINVAL
+    for bad_range in (-1, 32768):
+        with pytest.raises(IEError) as e:
+            codec.probe_gop(y, w, h, q64[:1], gop, bad_range, nframes=f)
+        assert e.value.code == IE_EINVAL
+    # no P-frame: ie_probe_sizes
+    np.testing.assert_array_equal(codec.probe_gop(y, w, h, q64[:7], 1, merange, nframes=f),
+                                  codec.probe_sizes(y, w, h, q64[:7], nframes=f))
+    np.testing.assert_array_equal(codec.probe_gop(y, w, h, q64[:7], 4, merange, nframes=1),
+                                  codec.probe_sizes(y, w, h, q64[:7], nframes=1))
+
+
+def test_fresh_context_has_no_block_size():
+    from imageencoder_amd import Codec
+    c = Codec(0)
+    try:
+        with pytest.raises(IEError) as e:
+            c.probe_gop(np.zeros((2, 16, 16), dtype=np.uint8), 16, 16, np.ones((1, 16), dtype=np.uint16), 2, 4, nframes=2)
+        assert e.value.code == IE_ENOQUANT
+    finally:
+        c.close()
+
+
+def test_rows_equal_the_librarys_own_encodes(codec):
+    n, w, h, f, gop, merange = 4, 64, 48, 7, 3, 16
+    qs = _candidates(n)
+    y = synth.frames("shiftA", w, h, f, seed=11)
+    codec.set_quant(_base(n), n)
+    got = codec.probe_gop(y, w, h, qs, gop, merange, nframes=f)
+    for m in (1, 7, len(qs) - 1):
+        codec.set_quant(qs[m], n)
+        for call, mode in ((codec.encode_gop, MODE_FAST), (codec.encode_gop, MODE_EXACT), (codec.encode_gop_groups, MODE_FAST)):
+            out = np.zeros(codec.gop_stream_bound(w, h, f, merange), dtype=np.uint8)
+            fb, _ = call(y, w, h, out, gop, merange, nframes=f, mode=mode)
+            np.testing.assert_array_equal(fb, got[m], err_msg=f"candidate {m}")
+    codec.set_quant(_base(n), n)
+
+
+def test_probe_leaves_the_context_untouched(codec):
+    n, w, h, f, gop, merange = 4, 64, 48, 5, 3, 16
+    q = _base(n)
+    y = synth.frames("P", w, h, f, seed=13)
+    codec.set_quant(q, n)
+
+    def encode():
+        out = np.zeros(codec.gop_stream_bound(w, h, f, merange), dtype=np.uint8)
+        fb, end = codec.encode_gop(y, w, h, out, gop, merange, nframes=f)
+        return out.tobytes(), fb.tolist(), end, codec.cos_table().tobytes()
+
+    before = encode()
+    got = codec.probe_gop(y, w, h, _candidates(n), gop, merange, nframes=f)
+    after = encode()
+    assert before == after
+    assert got[0].tolist() == before[1]  # candidate 0 is the context's own matrix
