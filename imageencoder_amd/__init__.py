@@ -98,6 +98,10 @@ def load_library(path: str | None = None) -> C.CDLL:
         L.ie_probe_gop.restype = C.c_int
         L.ie_probe_gop.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
                                    u16p, C.c_int, u64p]
+    if hasattr(L, "ie_probe_gop_rd"):  # (absent from an older IE_LIB build under comparison)
+        L.ie_probe_gop_rd.restype = C.c_int
+        L.ie_probe_gop_rd.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, u16p, C.c_int, u64p, u64p]
     for name in ("ie_huffman_hist", "ie_huffman_pack", "ie_bitcopy", "ie_decode_frames"):
         if hasattr(L, name):
             getattr(L, name).restype = C.c_int
@@ -193,6 +197,11 @@ def load_host_library(path: str | None = None) -> C.CDLL:
         H.ieh_encode_video_budget.restype = C.c_int64
         H.ieh_encode_video_budget.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, ip]
+    if hasattr(H, "ieh_encode_video_quality"):  # (absent from an older IE_LIB build under comparison)
+        H.ieh_encode_video_quality.restype = C.c_int64
+        H.ieh_encode_video_quality.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_size_t, ip,
+                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     H.ieh_encode_video.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, vp, C.c_size_t]
     H.ieh_encode_video_gop.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
@@ -665,6 +674,40 @@ class Codec:
                                      nq, bits.ctypes.data_as(u64p), sse.ctypes.data_as(u64p)))
         return bits, sse
 
+    def probe_gop_rd(self, y, w: int, h: int, qs, gop: int, merange: int, nframes: int = 1, rle: bool = True,
+                     motioncomp: bool = True, stride: int | None = None, frame_pitch: int | None = None, out=None):
+        """:meth:`probe_gop`, and the distortion with it (ie_probe_gop_rd): ``(bits, sse)``, each of
+        shape ``(nq, nframes)`` uint64.  ``sse[m, f]`` is the exact sum over frame f's pixels of
+        (decoded - original)^2, the decoded pixel being what :meth:`decode_gop` writes with this
+        ``motioncomp`` for the stream :meth:`encode_gop` writes after ``set_quant(qs[m])``.  With
+        P-frames, ``w`` and ``h`` are multiples of 16 and the blocks 4x4 (what does not decode has
+        nothing to measure: ``IE_EINVAL``).  The codec's own matrix is left as it was.  ``out``: an
+        optional pair ``(bits, sse)`` of device tensors of ``nq * nframes`` 64-bit entries each
+        (``bits`` may be None), which receive the sums instead -- the call is then asynchronous and
+        returns ``out``."""
+        stride = w if stride is None else stride
+        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        nn = (self.n or 0) ** 2
+        qs = np.ascontiguousarray(np.asarray(qs, dtype=np.uint16).reshape(-1, nn) if nn else
+                                  np.asarray(qs, dtype=np.uint16))
+        nq = qs.shape[0] if nn else 1
+        u64p = C.POINTER(C.c_uint64)
+        if out is not None:
+            dbits, dsse = out
+            if any(t is not None and _nbytes(t) < 8 * nq * nframes for t in (dbits, dsse)):
+                raise IEError(IE_EINVAL, "probe_gop_rd: out holds fewer than nq * nframes 64-bit entries")
+            self._chk(self.L.ie_probe_gop_rd(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, gop, merange, int(rle),
+                                             int(motioncomp), qs.ctypes.data, nq,
+                                             None if dbits is None else C.cast(C.c_void_p(_ptr(dbits)), u64p),
+                                             None if dsse is None else C.cast(C.c_void_p(_ptr(dsse)), u64p)))
+            return out
+        bits = np.zeros((max(nq, 1), nframes), dtype=np.uint64)
+        sse = np.zeros((max(nq, 1), nframes), dtype=np.uint64)
+        self._chk(self.L.ie_probe_gop_rd(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, gop, merange, int(rle),
+                                         int(motioncomp), qs.ctypes.data, nq, bits.ctypes.data_as(u64p),
+                                         sse.ctypes.data_as(u64p)))
+        return bits, sse
+
     def host_array(self, nbytes: int) -> np.ndarray:
         """A uint8 numpy array in page-locked host memory (ie_host_alloc): host buffers the
         streamed path DMAs directly.  Freed when the array (and the codec) are gone."""
@@ -854,6 +897,39 @@ class Codec:
             raise e
         self.n = n
         return out[: int(r)].tobytes(), int(pc.value)
+
+    def encode_video_quality(self, yuv, w: int, h: int, q, n: int, max_sse: int | None = None,
+                             psnr: float | None = None, gop: int = 1, merange: int = 0, motioncomp: bool = True,
+                             rle: bool = True, huffman: bool = True, mode: int = MODE_FAST):
+        """A video file (as :meth:`encode_video_file` writes it) with the coarsest probed scale of
+        ``q`` whose distortion -- the squared error of the decoded Y planes of all frames for a decoder
+        run with this ``motioncomp``, :meth:`probe_gop_rd` -- is at most ``max_sse``
+        (ieh_encode_video_quality): ``(bytes, percent, sse, frame_sse)``, ``frame_sse`` a uint64
+        array with every frame's share of ``sse``.  Exactly one of ``max_sse`` and ``psnr`` (dB,
+        turned into a squared error over ``frames * w * h`` pixels by :func:`sse_for_psnr`) is given.
+        Raises ``IEError(IE_ECAP, ...)`` (``e.percent`` = 25) when no scale meets it.  The codec's
+        matrix afterwards is the chosen one."""
+        if (max_sse is None) == (psnr is None):
+            raise IEError(IE_EINVAL, "encode_video_quality: give exactly one of max_sse and psnr")
+        frames = _nbytes(yuv) // (w * h + w * h // 2)
+        if max_sse is None:
+            max_sse = sse_for_psnr(psnr, frames * w * h)
+        H = load_host_library()
+        q = np.ascontiguousarray(np.asarray(q, dtype=np.uint16).ravel())
+        cap = stream_bound(w, h, n, max(frames, 1), 2048) + (w // 16) * (h // 16) * 4 * max(frames, 1) + 64
+        out = np.zeros(cap, dtype=np.uint8)
+        pc, se = C.c_int(0), C.c_uint64(0)
+        fse = np.zeros(max(frames, 1), dtype=np.uint64)
+        r = H.ieh_encode_video_quality(self.h, _ptr(yuv), _nbytes(yuv), w, h, q.ctypes.data, n, int(rle), int(huffman),
+                                       gop, merange, int(motioncomp), mode, min(max(int(max_sse), 0), 2 ** 64 - 1),
+                                       out.ctypes.data, cap, C.byref(pc), C.byref(se),
+                                       fse.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if r < 0:
+            e = IEError(int(r), self.L.ie_last_error(self.h).decode())
+            e.percent = int(pc.value)
+            raise e
+        self.n = n
+        return out[: int(r)].tobytes(), int(pc.value), int(se.value), fse[:frames]
 
     def encode_video_file(self, yuv, w: int, h: int, q, n: int, rle: bool = True, huffman: bool = True,
                           merange: int = 0, mode: int = MODE_FAST, gop: int = 1) -> bytes:

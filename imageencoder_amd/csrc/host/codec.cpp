@@ -694,9 +694,12 @@ const int kBudgetLadder[32] = {25,  30,  35,  42,  50,  59,  71,   84,   100,  1
 // File bytes (before any Huffman pass) of every percent in `pc` for one frame, and with `sse` the
 // squared error of the decoded frame: one ie_probe_sizes / ie_probe_rd call over the distinct
 // scaled matrices, mapped back to the percents.  A video file (p.video; sizes only): one
-// ie_probe_gop call over its frames' Y planes, the frames' bits summed.
+// ie_probe_gop call over its frames' Y planes, the frames' bits summed; with `sse` one ie_probe_gop_rd
+// call judged for the decoder setting `motioncomp`, the frames' errors summed and, with `frame_sse`,
+// kept per percent as well ([pc.size()][p.frames]).
 int probe_percents(ie_ctx* c, const uint8_t* y, dc::FileParams p, const uint16_t* base, const std::vector<int>& pc,
-                   std::vector<uint64_t>& bytes, std::vector<uint64_t>* sse = nullptr) {
+                   std::vector<uint64_t>& bytes, std::vector<uint64_t>* sse = nullptr, int motioncomp = 1,
+                   std::vector<uint64_t>* frame_sse = nullptr) {
     const int nn = p.n * p.n;
     std::vector<uint16_t> qs;        // the distinct matrices, in order of first use
     std::vector<int> which(pc.size());
@@ -712,13 +715,24 @@ int probe_percents(ie_ctx* c, const uint8_t* y, dc::FileParams p, const uint16_t
     const int nq = int(qs.size() / size_t(nn));
     std::vector<uint64_t> bits(static_cast<size_t>(nq), 0), se(static_cast<size_t>(nq), 0);
     int r;
+    std::vector<uint64_t> fse;  // a video's squared errors per matrix and frame
     if (p.video) {
         std::vector<uint64_t> fbits(static_cast<size_t>(nq) * size_t(p.frames), 0);
-        r = ie_probe_gop(c, y, p.w, p.h, size_t(p.w), p.frame_pitch, p.frames, p.gop, p.merange, p.rle ? 1 : 0, qs.data(),
-                         nq, fbits.data());
-        for (int m = 0; m < nq; m++)
+        if (sse) {
+            fse.assign(fbits.size(), 0);
+            r = ie_probe_gop_rd(c, y, p.w, p.h, size_t(p.w), p.frame_pitch, p.frames, p.gop, p.merange, p.rle ? 1 : 0,
+                                motioncomp, qs.data(), nq, fbits.data(), fse.data());
+        } else {
+            r = ie_probe_gop(c, y, p.w, p.h, size_t(p.w), p.frame_pitch, p.frames, p.gop, p.merange, p.rle ? 1 : 0,
+                             qs.data(), nq, fbits.data());
+        }
+        for (int m = 0; m < nq; m++) {
             bits[size_t(m)] = std::accumulate(fbits.begin() + size_t(m) * p.frames, fbits.begin() + size_t(m + 1) * p.frames,
                                               uint64_t(0));
+            if (sse)
+                se[size_t(m)] = std::accumulate(fse.begin() + size_t(m) * p.frames, fse.begin() + size_t(m + 1) * p.frames,
+                                                uint64_t(0));
+        }
     } else {
         r = sse ? ie_probe_rd(c, y, p.w, p.h, size_t(p.w), 0, 1, p.rle ? 1 : 0, qs.data(), nq, bits.data(), se.data())
                 : ie_probe_sizes(c, y, p.w, p.h, size_t(p.w), 0, 1, p.rle ? 1 : 0, qs.data(), nq, bits.data());
@@ -726,7 +740,11 @@ int probe_percents(ie_ctx* c, const uint8_t* y, dc::FileParams p, const uint16_t
     if (r) return r;
     bytes.resize(pc.size());
     if (sse) sse->resize(pc.size());
+    if (frame_sse) frame_sse->resize(pc.size() * size_t(p.frames));
     for (size_t i = 0; i < pc.size(); i++) {
+        if (frame_sse)
+            std::copy(fse.begin() + size_t(which[i]) * p.frames, fse.begin() + size_t(which[i] + 1) * p.frames,
+                      frame_sse->begin() + i * size_t(p.frames));
         p.q = qs.data() + size_t(which[i]) * nn;
         util::BitStreamWriter hdr(64);
         dc::write_header(hdr, p);  // (its length depends on the matrix's widest value)
@@ -821,6 +839,47 @@ int64_t encode_budget(ie_ctx* c, const uint8_t* dy, const dc::FileParams& p, con
     }
     return encode_scaled(c, dy, p, base, best, best_bytes, "budget", out, cap, percent);
 }
+
+// The quality search over device frames dy (an image, or a video's YUV420 frames: p.video, judged
+// for the decoder setting `motioncomp`): the ladder, the refinement above the entry found, the encode
+// of the largest percent whose squared error is at most max_sse.  frame_sse (videos, optional):
+// the chosen percent's error of every frame.
+int64_t encode_quality(ie_ctx* c, const uint8_t* dy, const dc::FileParams& p, const uint16_t* base, uint64_t max_sse,
+                       int motioncomp, uint8_t* out, size_t cap, int* percent, uint64_t* sse, uint64_t* frame_sse) {
+    int r;
+    const size_t nf = size_t(p.frames);
+    std::vector<int> ladder(kBudgetLadder, kBudgetLadder + 32);
+    std::vector<uint64_t> size, se, fr;
+    std::vector<uint64_t>* const pfr = frame_sse ? &fr : nullptr;
+    if ((r = probe_percents(c, dy, p, base, ladder, size, &se, motioncomp, pfr))) return r;
+    int i0 = -1;  // the largest ladder percent whose distortion meets the target
+    for (int i = 0; i < 32; i++)
+        if (se[size_t(i)] <= max_sse) i0 = i;
+    if (i0 < 0) {
+        *percent = kBudgetLadder[0];
+        ie_set_error(c, "no scale down to 25 % meets the quality");
+        return IE_ECAP;
+    }
+    int best = kBudgetLadder[i0];
+    uint64_t best_bytes = size[size_t(i0)], best_se = se[size_t(i0)];
+    if (frame_sse) std::copy(fr.begin() + size_t(i0) * nf, fr.begin() + size_t(i0 + 1) * nf, frame_sse);
+    if (i0 < 31) {  // the integers between it and the entry above, at most 32 of them
+        const std::vector<int> fine = refine_percents(kBudgetLadder[i0], kBudgetLadder[i0 + 1]);
+        if (!fine.empty()) {
+            std::vector<uint64_t> fsize, fse;
+            if ((r = probe_percents(c, dy, p, base, fine, fsize, &fse, motioncomp, pfr))) return r;
+            for (size_t i = 0; i < fine.size(); i++)  // (ascending: the last that meets it is the largest)
+                if (fse[i] <= max_sse) {
+                    best = fine[i];
+                    best_bytes = fsize[i];
+                    best_se = fse[i];
+                    if (frame_sse) std::copy(fr.begin() + i * nf, fr.begin() + (i + 1) * nf, frame_sse);
+                }
+        }
+    }
+    *sse = best_se;
+    return encode_scaled(c, dy, p, base, best, best_bytes, "quality", out, cap, percent);
+}
 }  // namespace
 
 int ieh_budget_ladder(int* out) {
@@ -869,34 +928,7 @@ int64_t ieh_encode_image_quality(ie_ctx* c, const uint8_t* y, int w, int h, cons
     p.mode = mode;
     const uint8_t* dy;
     if ((r = frame_on_device(c, y, w, h, &dy))) return r;
-    std::vector<int> ladder(kBudgetLadder, kBudgetLadder + 32);
-    std::vector<uint64_t> size, se;
-    if ((r = probe_percents(c, dy, p, base, ladder, size, &se))) return r;
-    int i0 = -1;  // the largest ladder percent whose distortion meets the target
-    for (int i = 0; i < 32; i++)
-        if (se[size_t(i)] <= max_sse) i0 = i;
-    if (i0 < 0) {
-        *percent = kBudgetLadder[0];
-        ie_set_error(c, "no scale down to 25 % meets the quality");
-        return IE_ECAP;
-    }
-    int best = kBudgetLadder[i0];
-    uint64_t best_bytes = size[size_t(i0)], best_se = se[size_t(i0)];
-    if (i0 < 31) {  // the integers between it and the entry above, at most 32 of them
-        const std::vector<int> fine = refine_percents(kBudgetLadder[i0], kBudgetLadder[i0 + 1]);
-        if (!fine.empty()) {
-            std::vector<uint64_t> fsize, fse;
-            if ((r = probe_percents(c, dy, p, base, fine, fsize, &fse))) return r;
-            for (size_t i = 0; i < fine.size(); i++)  // (ascending: the last that meets it is the largest)
-                if (fse[i] <= max_sse) {
-                    best = fine[i];
-                    best_bytes = fsize[i];
-                    best_se = fse[i];
-                }
-        }
-    }
-    *sse = best_se;
-    return encode_scaled(c, dy, p, base, best, best_bytes, "quality", out, cap, percent);
+    return encode_quality(c, dy, p, base, max_sse, 1, out, cap, percent, sse, nullptr);
 }
 
 int64_t ieh_encode_video(ie_ctx* c, const uint8_t* yuv, size_t len, int w, int h, const uint16_t* q, int n, int rle,
@@ -952,6 +984,30 @@ int64_t ieh_encode_video_budget(ie_ctx* c, const uint8_t* yuv, size_t len, int w
     const uint8_t* dy;
     if ((r = frames_on_device(c, yuv, size_t(p.frames) * p.frame_pitch, &dy))) return r;
     return encode_budget(c, dy, p, base, budget_bytes, out, cap, percent);
+}
+
+int64_t ieh_encode_video_quality(ie_ctx* c, const uint8_t* yuv, size_t len, int w, int h, const uint16_t* base, int n,
+                                 int rle, int huffman, int gop, int merange, int motioncomp, int mode, uint64_t max_sse,
+                                 uint8_t* out, size_t cap, int* percent, uint64_t* sse, uint64_t* frame_sse) {
+    if (!c || !yuv || !base || !out || !percent || !sse || (n != 4 && n != 8) || w <= 0 || h <= 0) return IE_EINVAL;
+    dc::FileParams p;
+    p.w = w;
+    p.h = h;
+    p.n = n;
+    p.rle = rle != 0;
+    p.huffman = huffman != 0;
+    p.mode = mode;
+    p.video = true;
+    p.frame_pitch = size_t(w) * h + size_t(w) * h / 2;
+    p.frames = int(len / p.frame_pitch);
+    p.gop = gop < 1 ? 1 : gop;
+    p.merange = merange;
+    if (p.frames <= 0 || p.frames > 32767) return IE_EINVAL;
+    int r;
+    if ((r = ie_set_quant(c, base, n))) return r;  // the probe's block size and transform tables
+    const uint8_t* dy;
+    if ((r = frames_on_device(c, yuv, size_t(p.frames) * p.frame_pitch, &dy))) return r;
+    return encode_quality(c, dy, p, base, max_sse, motioncomp, out, cap, percent, sse, frame_sse);
 }
 
 int64_t ieh_decode_image(ie_ctx* c, const uint8_t* enc, size_t len, int n, uint8_t* out, size_t cap, int* w, int* h) {

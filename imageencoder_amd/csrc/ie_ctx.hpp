@@ -246,6 +246,8 @@ struct ie_ctx {
     iec::Buf<uint64_t, iec::Mem::Pinned> h_probe_out;
     // ie_probe_gop: two reconstructed frames per (group, candidate) pair of one wave
     iec::Buf<uint8_t> d_probe_gop;
+    // ie_probe_gop_rd: four frames per pair -- two reconstructions, two decoded frames
+    iec::Buf<uint8_t> d_probe_gop_rd;
 };
 
 namespace iec {

@@ -143,11 +143,21 @@ struct ProbeArgs {
     const uint16_t* q;       // [nq][N*N] candidates in ZIG-ZAG order (device)
     const EncTables* tab;    // P, S and R of the block size (they do not depend on the matrix)
     unsigned long long* bits;  // [nq][nframes], zero before the launch: bits[m * nframes + f] is added to
+    // launch_probe_rd_store alone (ie_probe_gop_rd's I-frames; the other launches never read these):
+    // the sums of candidate m, frame f are added to bits / sse [m * out_m + f * out_f], and the
+    // decoded pixels of the first dec_frames frames go to dec + f * f_dec + m * m_dec, [h][w] packed
+    uint64_t out_m, out_f;
+    uint8_t* dec;
+    uint64_t f_dec, m_dec;
+    int dec_frames;
 };
 void launch_probe_sizes(const ProbeArgs& a, int n, hipStream_t s);
 // the distortion too: sse has the shape and rule of bits, which may then be nullptr
 void launch_probe_rd(const ProbeArgs& a, unsigned long long* sse, int n, hipStream_t s);
 int probe_rd_max_workgroups(int n);  // the grid of launch_probe_rd is min(tiles, this)
+// launch_probe_rd for 4x4 blocks that also stores every candidate's decoded pixels (the fields
+// above): four pixels to a store, so w % 4 == 0 and dec, f_dec, m_dec multiples of 4
+void launch_probe_rd_store(const ProbeArgs& a, unsigned long long* sse, hipStream_t s);
 
 struct PackArgs {            // Huffman re-encode / bit copy: one variable-length code per byte
     const uint8_t* in;
@@ -396,6 +406,19 @@ struct PgArgs {
     uint64_t m_bits, g_bits;
 };
 void launch_pframe_probe(const PgArgs& a, int groups, hipStream_t s);
+// ie_probe_gop_rd: the same step carrying the decoder's frame chain next to the encoder's.  W and
+// H are multiples of 16 (no uncovered strips).  Candidate m of group g copies its blocks from its
+// own DECODED previous frame, dref + g * g_dec + m * m_dec, and leaves this frame's decoded pixels
+// in dec + g * g_dec + m * m_dec (both [h][w]; dec == nullptr: not stored); the squared error
+// against cur is added to sse[m * m_bits + g * g_bits].  bits may be nullptr here.
+struct PgRdArgs : PgArgs {
+    const uint8_t* dref;
+    uint8_t* dec;
+    uint64_t g_dec, m_dec;
+    int motioncomp;          // 0: the decoder copies the blocks and drops the error
+    unsigned long long* sse;
+};
+void launch_pframe_probe_rd(const PgRdArgs& a, int groups, hipStream_t s);
 // dst[m * nframes + g * gop] = src[m * groups + g] (the I-frames' sums); fill: every other entry = pconst
 void launch_pframe_probe_scatter(const unsigned long long* src, unsigned long long* dst, int nq, int nframes, int gop,
                                  int groups, int fill, unsigned long long pconst, hipStream_t s);

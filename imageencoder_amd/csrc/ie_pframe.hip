@@ -18,8 +18,11 @@
 // run one frame of many groups of pictures at once (blockIdx.y = the group, each with a stream slot
 // of its own); gop_splice_kernel then moves the slots' payloads end to end (ie_encode_gop_groups).
 // pf_probe_kernel is the macroblock pass under many candidate matrices with nothing emitted: the
-// P-frame sizes of ie_probe_gop.
+// P-frame sizes of ie_probe_gop; instantiated over PgRdArgs it also forms the pixels the decoder would
+// write and their squared error (ie_probe_gop_rd).
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "ie_common.hpp"
 #include "ie_device.h"
@@ -583,7 +586,16 @@ __device__ __forceinline__ PfVec pf_search(uint32_t c4, const uint8_t* ref, uint
     return PfVec{cx, cy, bbx, bby};
 }
 
-__global__ __launch_bounds__(kMbTPB) void pf_probe_kernel(PgArgs a) {
+// A = PgRdArgs (ie_probe_gop_rd) carries the decoder's frame chain next to the encoder's.  The
+// pixels a viewer sees are not the pixels the encoder predicts from: the decoder copies its blocks
+// from its own previous frame (which goes back to the LOSSY decoded I-frame), at the vector as the
+// stream holds it, and adds the error it reads from the record -- after the one lossy rule of the
+// stream (size4: with RLE a record of length 16 whose zig-zag value 14 is zero loses its last
+// value).  That value is coefficient 15, the last term of the uv-ascending inverse sum, so the
+// decoder's sum is the encoder's partial sum before that term (the term it adds instead is +-0).
+template <class A>
+__global__ __launch_bounds__(kMbTPB) void pf_probe_kernel(A a) {
+    constexpr bool RD = std::is_same<A, PgRdArgs>::value;
     __shared__ double xs[256];
     __shared__ double Ps[256], Rs[256], Ss[16];
     __shared__ int16_t cq[256];
@@ -632,6 +644,7 @@ __global__ __launch_bounds__(kMbTPB) void pf_probe_kernel(PgArgs a) {
     PfVec v{0, 0, 0, 0};
     double D[4] = {0.0, 0.0, 0.0, 0.0};      // acc * S of the lane's coefficients
     uint32_t mine = 0;                       // lane i: the macroblock's bits under candidate m0 + i
+    uint32_t mine_se = 0;                    // RD, lane i: its squared error (<= 256 * 255^2)
     for (int i = 0; i < cnt; i++) {
         const uint8_t* ref = ref0 + uint64_t(i) * a.m_ref;
         if (i == 0 || !shared) {
@@ -663,27 +676,62 @@ __global__ __launch_bounds__(kMbTPB) void pf_probe_kernel(PgArgs a) {
         const uint32_t len = gq == 0 ? rec_len(size4(cq + m * 16, a.rle), a.rle) : 0u;
         const uint32_t sum = wave_sum(len) + 2u * uint32_t(a.mv_bits);
         if (l == i) mine = sum;
-        if (!rec0) continue;  // (wave-uniform) the group's last P-frame: nothing reads its reconstruction
+        if (!RD && !rec0) continue;  // (wave-uniform) the group's last P-frame: nothing reads its reconstruction
         // ---- inverse + expandDifferences, as the encode kernel: lane = (microblock l/4, pixel row l%4)
+        // (the last term apart: the decoder's sum may end before it)
         double tt[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int uv = 0; uv < 16; uv++) {
+        for (int uv = 0; uv < 15; uv++) {
             const double yv = double(cq[m * 16 + uv]) * qs[uv];
 #pragma unroll
             for (int j = 0; j < 4; j++) tt[j] = tt[j] + Rs[uv * 16 + gq + j] * yv;
         }
+        const double y15 = double(cq[m * 16 + 15]) * qs[15];
         const int ccx = clamp16(mx + v.cx, W16), ccy = clamp16(my + v.cy, H16);
         const int ppy = (m >> 2) * 4 + (l & 3), ppx = (m & 3) * 4;
-        const uint32_t b4 = load4(ref + size_t(ccy + ppy) * a.rs + ccx + ppx);
-        uint32_t o4 = 0;
+        if (rec0) {
+            const uint32_t b4 = load4(ref + size_t(ccy + ppy) * a.rs + ccx + ppx);
+            uint32_t o4 = 0;
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const double vv = double(int((b4 >> (8 * j)) & 255u)) + (tt[j] + double(128));
-            o4 |= uint32_t(uint8_t(vv < 0.0 ? 0.0 : (vv > 255.0 ? 255.0 : vv))) << (8 * j);
+            for (int j = 0; j < 4; j++) {
+                const double vv = double(int((b4 >> (8 * j)) & 255u)) + ((tt[j] + Rs[15 * 16 + gq + j] * y15) + double(128));
+                o4 |= uint32_t(uint8_t(vv < 0.0 ? 0.0 : (vv > 255.0 ? 255.0 : vv))) << (8 * j);
+            }
+            *reinterpret_cast<uint32_t*>(rec0 + uint64_t(i) * a.m_rec + size_t(my + ppy) * a.w + mx + ppx) = o4;
         }
-        *reinterpret_cast<uint32_t*>(rec0 + uint64_t(i) * a.m_rec + size_t(my + ppy) * a.w + mx + ppx) = o4;
+        if constexpr (RD) {
+            // the record as the decoder reads it (the length rule of size4)
+            const bool cut = a.rle && cq[m * 16 + 15] != 0 && cq[m * 16 + 14] == 0;
+            // the vector as the decoder reads it: mv_bits bits, sign-extended (pf_mvcopy_kernel)
+            const int sh = 16 - a.mv_bits;
+            const int vx = int(int16_t(uint16_t(uint32_t(v.cx) << sh)) >> sh), vy = int(int16_t(uint16_t(uint32_t(v.cy) << sh)) >> sh);
+            const int dcx = clamp16(mx + vx, W16), dcy = clamp16(my + vy, H16);
+            const uint64_t pair = g * a.g_dec + uint64_t(m0 + i) * a.m_dec;
+            const uint32_t p4 = load4(a.dref + pair + size_t(dcy + ppy) * a.w + dcx + ppx);
+            const uint32_t s4 = load4(cur + size_t(my + ppy) * a.cs + mx + ppx);
+            uint32_t d4 = p4, se = 0;
+            if (a.motioncomp) d4 = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                int d = int((p4 >> (8 * j)) & 255u);
+                if (a.motioncomp) {  // expandDifferences, the operation order of decode_record (ie_decode.hip)
+                    double x = (cut ? tt[j] : tt[j] + Rs[15 * 16 + gq + j] * y15) + 128.0;
+                    x = double(d) + x;
+                    d = int(uint8_t(x < 0.0 ? 0.0 : (x > 255.0 ? 255.0 : x)));
+                    d4 |= uint32_t(d) << (8 * j);
+                }
+                const int e = d - int((s4 >> (8 * j)) & 255u);
+                se += uint32_t(e * e);
+            }
+            if (a.dec) *reinterpret_cast<uint32_t*>(a.dec + pair + size_t(my + ppy) * a.w + mx + ppx) = d4;
+            se = wave_sum(se);
+            if (l == i) mine_se = se;
+        }
     }
-    if (l < cnt) atomicAdd(a.bits + uint64_t(m0 + l) * a.m_bits + g * a.g_bits, (unsigned long long)mine);
+    if (l < cnt) {
+        if (!RD || a.bits) atomicAdd(a.bits + uint64_t(m0 + l) * a.m_bits + g * a.g_bits, (unsigned long long)mine);
+        if constexpr (RD) atomicAdd(a.sse + uint64_t(m0 + l) * a.m_bits + g * a.g_bits, (unsigned long long)mine_se);
+    }
 }
 
 // ie_probe_gop: the I-frames' sums (src[m * groups + g], ie_probe_sizes' layout over the I-frames
@@ -707,8 +755,16 @@ void launch_pframe_probe(const PgArgs& a, int groups, hipStream_t s) {
     const unsigned grid = unsigned(nmb) + unsigned((px + kMbTPB - 1) / kMbTPB);
     const unsigned gz = unsigned((a.nm + a.mper - 1) / a.mper);
     if (grid)
-        hipLaunchKernelGGL(pf_probe_kernel, dim3(grid, unsigned(groups), gz), dim3(kMbTPB), size_t(a.mper) * 16 * sizeof(double),
-                           s, a);
+        hipLaunchKernelGGL(pf_probe_kernel<PgArgs>, dim3(grid, unsigned(groups), gz), dim3(kMbTPB),
+                           size_t(a.mper) * 16 * sizeof(double), s, a);
+}
+
+void launch_pframe_probe_rd(const PgRdArgs& a, int groups, hipStream_t s) {
+    const unsigned grid = unsigned(a.mbx * a.mby);  // W and H are multiples of 16: no strips
+    const unsigned gz = unsigned((a.nm + a.mper - 1) / a.mper);
+    if (grid)
+        hipLaunchKernelGGL(pf_probe_kernel<PgRdArgs>, dim3(grid, unsigned(groups), gz), dim3(kMbTPB),
+                           size_t(a.mper) * 16 * sizeof(double), s, a);
 }
 
 void launch_pframe_probe_scatter(const unsigned long long* src, unsigned long long* dst, int nq, int nframes, int gop,

@@ -132,8 +132,9 @@ __device__ __forceinline__ void probe_idct4_terms(uint32_t any, int ylo, int yhi
 //    ascending order, four per trip (the R reads of a trip are issued together; a trip's missing
 //    terms are Y = 0 at uv = 0).  Y[uv] is a readlane: the multiply takes it from SGPRs.
 //  - 4x4: four blocks, one per DPP row; a term is skipped when it is zero in all four.
+// d8 receives the decoded byte itself (the store of probe_kernel<N, true, true>).
 template <int N>
-__device__ __forceinline__ uint32_t probe_rd_sse(int vd, double qd, const double* Rl, uint32_t px, int lane) {
+__device__ __forceinline__ uint32_t probe_rd_sse(int vd, double qd, const double* Rl, uint32_t px, int lane, uint32_t& d8) {
     constexpr int NN = N * N;
     const double Y = double(vd) * qd;
     int ylo = __double2loint(Y), yhi = __double2hiint(Y);
@@ -163,13 +164,18 @@ __device__ __forceinline__ uint32_t probe_rd_sse(int vd, double qd, const double
     }
     double x = t + 128.0;
     x = x < 0.0 ? 0.0 : (x > 255.0 ? 255.0 : x);
-    const int err = int(uint8_t(x)) - int(px);  // in [-255, 255]
+    d8 = uint32_t(uint8_t(x));
+    const int err = int(d8) - int(px);  // in [-255, 255]
     return uint32_t(err * err);
 }
 
-// RD = false: the sizes alone (ie_probe_sizes); RD = true: the distortion too (ie_probe_rd)
-template <int N, bool RD>
+// RD = false: the sizes alone (ie_probe_sizes); RD = true: the distortion too (ie_probe_rd).
+// ST (ie_probe_gop_rd's I-frames): the sums go to [m * out_m + f * out_f], and every candidate's
+// decoded pixels of the frames before dec_frames are stored -- the lane of a block row's first
+// pixel collects its quad's four bytes by DPP and writes one word.
+template <int N, bool RD, bool ST = false>
 __global__ __launch_bounds__(kTPB) void probe_kernel(ProbeArgs a, unsigned long long* sse) {
+    static_assert(!ST || RD, "only the distortion pass decodes pixels");
     using G = ProbeGeo<N>;
     constexpr int NN = G::NN, BPW = G::BPW, TB = G::TB;
     extern __shared__ __attribute__((aligned(16))) unsigned char probe_lds[];
@@ -200,16 +206,17 @@ __global__ __launch_bounds__(kTPB) void probe_kernel(ProbeArgs a, unsigned long 
     uint64_t mine_se = 0;
     int64_t cur_f = -1;
     const bool owner = kz == NN - 1;  // the block's last lane holds its DPP results
+    const auto sum_index = [&](int m, int64_t f) {  // candidate m's sum of frame f
+        return ST ? uint64_t(m) * a.out_m + uint64_t(f) * a.out_f : uint64_t(m) * uint64_t(a.nframes) + uint64_t(f);
+    };
 
     for (uint64_t it = blockIdx.x; it < total; it += gridDim.x) {
         const int64_t f = int64_t(it / tpf);
         const int b0 = int(it % tpf) * TB;
         if (f != cur_f) {
             if (cur_f >= 0 && lane < a.nq) {
-                if (!RD || a.bits)
-                    atomicAdd(&a.bits[uint64_t(lane) * uint64_t(a.nframes) + uint64_t(cur_f)], (unsigned long long)mine);
-                if constexpr (RD)
-                    atomicAdd(&sse[uint64_t(lane) * uint64_t(a.nframes) + uint64_t(cur_f)], (unsigned long long)mine_se);
+                if (!RD || a.bits) atomicAdd(&a.bits[sum_index(lane, cur_f)], (unsigned long long)mine);
+                if constexpr (RD) atomicAdd(&sse[sum_index(lane, cur_f)], (unsigned long long)mine_se);
             }
             mine = 0;
             mine_se = 0;
@@ -260,6 +267,15 @@ __global__ __launch_bounds__(kTPB) void probe_kernel(ProbeArgs a, unsigned long 
             const double D = acc * S;
             uint32_t px = 0;  // RD: the byte of the lane's pixel (pixel kz of block j), before the level shift
             if constexpr (RD) px = (pixw[(kz >> 2) * TB + j] >> (8 * (kz & 3))) & 0xFFu;
+            // ST: where the lane's quad of decoded pixels goes (row kz / N of block j, from column kz % N),
+            // written by the quad's first lane
+            uint8_t* dst = nullptr;
+            if constexpr (ST) {
+                if (valid && (lane & 3) == 0 && f < a.dec_frames) {
+                    const int blk = b0 + j, byi = blk / a.bx, bxi = blk - byi * a.bx;
+                    dst = a.dec + uint64_t(f) * a.f_dec + (uint64_t(byi * N + kz / N) * uint64_t(a.bx) + uint64_t(bxi)) * N + kz % N;
+                }
+            }
 #pragma unroll 1
             for (int m = 0; m < a.nq; m++) {
                 const double qd = double(qz[m * NN + kz]);
@@ -296,7 +312,17 @@ __global__ __launch_bounds__(kTPB) void probe_kernel(ProbeArgs a, unsigned long 
                     // what the decoder reads: v, but the last value of a record RLE cut short (L == NN, value
                     // NN - 2 zero: lw above; Block.cpp:388-390) is 0
                     const int vd = (a.rle && L == uint32_t(NN) && lw != L && owner) ? 0 : v;
-                    const uint32_t se = probe_rd_sse<N>(vd, qd, Rn + kz, px, lane);
+                    uint32_t d8;
+                    const uint32_t se = probe_rd_sse<N>(vd, qd, Rn + kz, px, lane, d8);
+                    if constexpr (ST) {
+                        if (f < a.dec_frames) {  // (wave-uniform: every lane takes part in the quad broadcasts)
+                            const int d = int(d8);
+                            const uint32_t w4 = d8 | uint32_t(__builtin_amdgcn_update_dpp(0, d, 0x55, 0xf, 0xf, false)) << 8 |
+                                                uint32_t(__builtin_amdgcn_update_dpp(0, d, 0xAA, 0xf, 0xf, false)) << 16 |
+                                                uint32_t(__builtin_amdgcn_update_dpp(0, d, 0xFF, 0xf, 0xf, false)) << 24;
+                            if (dst) *reinterpret_cast<uint32_t*>(dst + uint64_t(m) * a.m_dec) = w4;
+                        }
+                    }
                     const uint32_t ssum = probe_wave_sum(valid ? se : 0u);  // <= 64 * 255^2
                     if (lane == m) mine_se += ssum;
                 }
@@ -304,10 +330,8 @@ __global__ __launch_bounds__(kTPB) void probe_kernel(ProbeArgs a, unsigned long 
         }
     }
     if (cur_f >= 0 && lane < a.nq) {
-        if (!RD || a.bits)
-            atomicAdd(&a.bits[uint64_t(lane) * uint64_t(a.nframes) + uint64_t(cur_f)], (unsigned long long)mine);
-        if constexpr (RD)
-            atomicAdd(&sse[uint64_t(lane) * uint64_t(a.nframes) + uint64_t(cur_f)], (unsigned long long)mine_se);
+        if (!RD || a.bits) atomicAdd(&a.bits[sum_index(lane, cur_f)], (unsigned long long)mine);
+        if constexpr (RD) atomicAdd(&sse[sum_index(lane, cur_f)], (unsigned long long)mine_se);
     }
 }
 
@@ -324,6 +348,14 @@ void launch_probe_sizes(const ProbeArgs& a, int n, hipStream_t s) {
 }
 
 int probe_rd_max_workgroups(int n) { return n == 4 ? 1024 : 512; }
+
+void launch_probe_rd_store(const ProbeArgs& a, unsigned long long* sse, hipStream_t s) {
+    const uint64_t total = uint64_t((a.bx * a.by + ProbeGeo<4>::TB - 1) / ProbeGeo<4>::TB) * uint64_t(a.nframes);
+    const uint64_t cap = uint64_t(probe_rd_max_workgroups(4));
+    if (total)
+        hipLaunchKernelGGL((probe_kernel<4, true, true>), dim3(unsigned(total < cap ? total : cap)), dim3(kTPB),
+                           ProbeGeo<4>::lds_bytes(a.nq, true), s, a, sse);
+}
 
 void launch_probe_rd(const ProbeArgs& a, unsigned long long* sse, int n, hipStream_t s) {
     const int tb = n == 4 ? ProbeGeo<4>::TB : ProbeGeo<8>::TB;

@@ -239,6 +239,40 @@ int ie_probe_rd(ie_ctx* ctx, const uint8_t* y, int w, int h, size_t stride, size
 int ie_probe_gop(ie_ctx* ctx, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,
                  int gop, int merange, int use_rle, const uint16_t* q, int nq, uint64_t* bits);
 
+/* ---- Distortion probe for videos with P-frames: ie_probe_rd's question for ie_encode_gop +
+ * ie_decode_gop.
+ *   y .. use_rle, q, nq   as ie_probe_gop: the same checks, order and codes.  Then: a call with
+ *                P-frames (gop > 1 and nframes > 1) needs W % 16 == 0 and H % 16 == 0 (ie_decode_gop's
+ *                rule: what it refuses has no decoded pixels), and 4x4 blocks -- an 8x8 P-frame
+ *                stream does not decode (ie_encode_gop writes no microblock records there,
+ *                ie_decode_gop reads one per microblock), so there is nothing to measure: IE_EINVAL.
+ *   motioncomp   the decoder setting the result is judged for, as in ie_decode_gop
+ *   sse          required: nq * nframes entries, host or device (8-byte aligned) memory
+ *   bits         optional (NULL: not wanted): receives exactly what ie_probe_gop writes.  bits and
+ *                sse are both host or both device memory: a mix is IE_EINVAL.
+ * sse[m*nframes + f] = the sum over frame f's w*h pixels of (d - y)^2, d the pixel that
+ * ie_decode_gop(.., gop, merange, use_rle, motioncomp, ..) writes for the stream that ie_encode_gop
+ * writes after ie_set_quant(ctx, q + m*n*n, n), in either mode: an exact integer.  gop <= 1 or
+ * nframes == 1 is ie_probe_rd.
+ * The decoder's frames are not the encoder's reconstructions.  The encoder's first P-frame of a
+ * group predicts from the I-frame's source, the decoder copies from the lossy decoded I-frame; the
+ * encoder rebuilds a P-frame from the quantised values, the decoder from the record after the one
+ * lossy rule of the stream (see ie_probe_rd); the decoder reads the vector in bits(merange) bits.
+ * So the probe carries both chains per candidate: the I-frames go through ie_probe_rd's kernel,
+ * which also stores every candidate's decoded pixels; the P-frames through ie_probe_gop's macroblock
+ * pass, which also forms the decoder's pixel (motioncomp: copied + (sum + 128), clamped and
+ * truncated; else the copied pixel) and adds its squared error.
+ *  - Scratch: four frames per (group, candidate) pair -- two reconstructions, two decoded frames --
+ *    in a buffer of its own.  The 1 GiB wave rule and IE_PROBE_GOP_MAX work as in ie_probe_gop and
+ *    never change a result.  The launches are as deep as gop.
+ *  - Device results: asynchronous on the context's stream.  Host results: one synchronisation and
+ *    one read-back.
+ *  - The context's matrix, tables, chain state, ie_last_end_bits, the encoders' gop scratch and
+ *    ie_probe_gop's scratch are left as they were. */
+int ie_probe_gop_rd(ie_ctx* ctx, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,
+                    int gop, int merange, int use_rle, int motioncomp, const uint16_t* q, int nq,
+                    uint64_t* bits, uint64_t* sse);
+
 /* ---- Device memory on the context's stream (for hosts that keep streams device-resident
  * between stages, e.g. the host library's encode -> Huffman pipeline).  ie_memcpy infers the
  * direction of each pointer and is asynchronous only when both are device memory. */

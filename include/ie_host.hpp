@@ -397,6 +397,19 @@ int64_t ieh_encode_video_gop(ie_ctx* ctx, const uint8_t* yuv, size_t len, int w,
 int64_t ieh_encode_video_budget(ie_ctx* ctx, const uint8_t* yuv, size_t len, int w, int h, const uint16_t* base,
                                 int n, int rle, int huffman, int gop, int merange, int mode, size_t budget_bytes,
                                 uint8_t* out, size_t cap, int* percent);
+// Whole video file (exactly as ieh_encode_video_gop writes it) with the COARSEST probed scale of
+// `base` whose distortion is at most max_sse: ieh_encode_image_quality's contract, search, error
+// codes, messages and context state for a video.  The distortion judged is the sum over all frames
+// of ie_probe_gop_rd's sse (Y planes only) for the decoder setting `motioncomp`; the sizes come
+// along in the same two probe calls.  *sse: the chosen scale's total; frame_sse (optional): its
+// error of every frame, len / (1.5 w h) entries -- the total hides that the late frames of a group
+// drift worst.  The frames lie 1.5 w h bytes apart; host frames go to the device once, for both
+// probes and the encode.  What ie_probe_gop_rd refuses (P-frames with W or H no multiple of 16, or
+// with 8x8 blocks) is IE_EINVAL here.
+int64_t ieh_encode_video_quality(ie_ctx* ctx, const uint8_t* yuv, size_t len, int w, int h, const uint16_t* base,
+                                 int n, int rle, int huffman, int gop, int merange, int motioncomp, int mode,
+                                 uint64_t max_sse, uint8_t* out, size_t cap, int* percent, uint64_t* sse,
+                                 uint64_t* frame_sse);
 // Decode an image file (host buffer) with block size n: pixels into out (w*h bytes).  A cap
 // below w*h returns IE_ECAP with *w / *h set, right after the header (the payload is not decoded):
 // call with cap = 0 to size the buffer.

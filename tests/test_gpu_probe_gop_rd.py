@@ -1,0 +1,333 @@
+"""GPU: ie_probe_gop_rd (Codec.probe_gop_rd) against the CPU oracle.  The truth for candidate m is
+oracle.encode_video_gop under qs[m], that file through oracle.decode_video_gop with the motioncomp
+under test, and the squared error of every decoded Y plane in numpy; bits is held against
+oracle.encode_gop as in tests/test_gpu_probe_gop.py.  Every comparison is of integers and exact.
+
+Shapes are the smallest that reach each way the kernel can go wrong: one macroblock with a ragged
+last group (16 x 16 x 5, gop 3), a shared first step followed by two steps of per-candidate chains
+(32 x 32 x 4, gop 4, every candidate in one call), 48 macroblocks x 2 groups whose atomics meet in
+one sum (128 x 96 x 6), padded rows and frames, waves of groups and chunks of candidates
+(IE_PROBE_GOP_MAX).  Coverage guards assert on the oracle's data that the inputs reach what they
+are meant to: the truncation rule of the stream fires, the decoder's chain drifts from the
+encoder's, a vector is non-zero.
+
+8x8 blocks with P-frames: one might expect their decoded pixels to be the decoded previous frame's
+blocks copied at the searched vectors, and their truth to come from oracle.decode_video_gop.
+Neither exists.  ie_encode_gop writes no microblock records for an 8x8
+P-frame and every decoder (the reference's, the oracle's, ie_decode_gop) reads one per microblock,
+so the decode parses the following frames' bits as records: for the 32 x 32 x 5 and 48 x 48 x 5,
+gop 3 videos of this file ieo_decode_video_gop returns -4 (a record longer than 64 values) under
+every candidate, with motion compensation on and off (see also tests/test_gpu_vdec.py::test_8x8_blocks).
+test_8x8_pframes_have_no_decode asserts exactly that, and that the probe refuses the call with
+IE_EINVAL rather than return a number no decoder produces; 8x8 without P-frames is ie_probe_rd."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from imageencoder_amd import IE_EINVAL, IE_ENOQUANT, MODE_EXACT, MODE_FAST, IEError, scale_matrix, synth
+from tests import matrix_sweep as MS
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def codec():
+    from imageencoder_amd import Codec
+    return Codec(0)
+
+
+def _base(n):
+    return MS.by_name(n, "jpeg_like" if n == 4 else "annex_k")
+
+
+def _candidates(n):
+    """The context's own matrix first, the sweep, the base scaled across the budget ladder's range."""
+    qs = [_base(n)] + [q for _, q in MS.sweep(n)] + [scale_matrix(_base(n), p) for p in (25, 59, 336, 1345, 5382)]
+    assert len(qs) <= 64
+    return np.stack(qs)
+
+
+def _few(n):
+    return _candidates(n)[[0, 2, -5, -2, -1]]
+
+
+def _contents(n, f, h, w):
+    return [("noise", synth.frames("U", w, h, f, seed=31)), ("shift", synth.frames("shiftA", w, h, f, seed=5)),
+            ("flat", synth.frames("flat128", w, h, f)), ("ties", MS.tie_frames(n, _base(n), w, h, f, seed=2))]
+
+
+def _decoded(oracle, y, n, q, gop, merange, rle, motioncomp):
+    """The Y planes oracle.decode_video_gop writes for oracle.encode_video_gop's file: (f, h, w) int64."""
+    f, h, w = y.shape
+    enc = oracle.encode_video_gop(synth.yuv420(y), w, h, n, q, rle=rle, huffman=False, gop=gop, merange=merange)
+    dec = np.frombuffer(oracle.decode_video_gop(enc, n, motioncomp), dtype=np.uint8)
+    return dec.reshape(f, w * h + w * h // 2)[:, : w * h].reshape(f, h, w).astype(np.int64)
+
+
+def _sse(dec, y):
+    return ((dec - y.astype(np.int64)) ** 2).reshape(len(y), -1).sum(axis=1).astype(np.uint64)
+
+
+def _truth(oracle, y, n, qs, gop, merange, rle=True, motioncomp=True):
+    return np.stack([_sse(_decoded(oracle, y, n, q, gop, merange, rle, motioncomp), y) for q in qs])
+
+
+def _bits(oracle, y, n, qs, gop, merange, rle=True, **layout):
+    return np.stack([oracle.encode_gop(y, n, q, gop, merange, rle=rle, **layout)[2] for q in qs]).astype(np.uint64)
+
+
+def _check(got, exp, what):
+    assert got.dtype == np.uint64 and got.shape == exp.shape
+    bad = np.argwhere(got != exp)
+    assert bad.size == 0, (what, "candidate, frame:", bad[:4].tolist(), got[bad[0][0]], exp[bad[0][0]])
+
+
+@pytest.mark.parametrize("motioncomp", [True, False], ids=["mc", "nomc"])
+@pytest.mark.parametrize("rle", [True, False], ids=["rle", "norle"])
+@pytest.mark.parametrize("merange", [0, 1, 16])
+def test_one_macroblock_ragged_last_group(codec, oracle, merange, rle, motioncomp):
+    n, w, h, f, gop = 4, 16, 16, 5, 3
+    qs = _candidates(n)
+    codec.set_quant(_base(n), n)
+    for kind, y in _contents(n, f, h, w):
+        bits, sse = codec.probe_gop_rd(y, w, h, qs, gop, merange, nframes=f, rle=rle, motioncomp=motioncomp)
+        _check(sse, _truth(oracle, y, n, qs, gop, merange, rle, motioncomp), kind + " sse")
+        _check(bits, _bits(oracle, y, n, qs, gop, merange, rle), kind + " bits")
+
+
+def _copied_from_source(oracle, y, n, q, gop, merange, f):
+    """P-frame f's macroblocks copied from the SOURCE of frame f - 1 at the vectors the decoder reads."""
+    _, h, w = y.shape
+    buf, _, fb = oracle.encode_gop(y, n, q, gop, merange)
+    out = np.zeros((h, w), dtype=np.int64)
+    vec = oracle.gop_vectors(buf, fb, 0, f, w, h, merange)
+    for mb, (vx, vy) in enumerate(vec):
+        mx, my = (mb % (w // 16)) * 16, (mb // (w // 16)) * 16
+        cx, cy = min(max(mx + vx, 0), w - 16), min(max(my + vy, 0), h - 16)
+        out[my: my + 16, mx: mx + 16] = y[f - 1, cy: cy + 16, cx: cx + 16]
+    return out, vec
+
+
+def test_shared_first_step_then_chained_decodes(codec, oracle):
+    """32 x 32 x 4, gop 4, every candidate in one call: step 1 shares the encoder's reference but not
+    the decoder's, steps 2 and 3 chain every candidate's own reconstruction and decoded frame."""
+    n, w, h, f, gop, merange = 4, 32, 32, 4, 4, 16
+    qs = _candidates(n)
+    codec.set_quant(_base(n), n)
+    for kind, y in _contents(n, f, h, w):
+        for mc in (True, False):
+            exp = _truth(oracle, y, n, qs, gop, merange, True, mc)
+            bits, sse = codec.probe_gop_rd(y, w, h, qs, gop, merange, nframes=f, motioncomp=mc)
+            _check(sse, exp, f"{kind} mc={mc}")
+            _check(bits, _bits(oracle, y, n, qs, gop, merange), kind)
+            if kind == "noise":  # the candidates do differ, on the P-frames too
+                assert len({tuple(r[1:]) for r in exp.tolist()}) > len(qs) // 2
+    # ---- coverage guards, on the oracle's data alone
+    y = dict(_contents(n, f, h, w))["noise"]
+    # the truncation rule fires: it is the only difference between the rle and the no-rle stream's decode
+    fired = [m for m, q in enumerate(qs)
+             if (_decoded(oracle, y, n, q, gop, merange, True, True)[1:] != _decoded(oracle, y, n, q, gop, merange, False, True)[1:]).any()]
+    assert fired, "no candidate's P-frame record loses its last value under RLE"
+    # the decoder's chain drifts from the encoder's: without motion compensation the first P-frame is the
+    # decoded I-frame's blocks; a probe that read the encoder's chain would copy the source's instead
+    truth0 = _truth(oracle, y, n, qs, gop, merange, True, False)
+    drift = sum(int(truth0[m, 1]) != int(((_copied_from_source(oracle, y, n, q, gop, merange, 1)[0] - y[1]) ** 2).sum())
+                for m, q in enumerate(qs))
+    assert 2 * drift >= len(qs), drift
+    # a vector of the shifted content is non-zero
+    ys = dict(_contents(n, f, h, w))["shift"]
+    assert any(v != (0, 0) for v in _copied_from_source(oracle, ys, n, _base(n), gop, merange, 1)[1])
+
+
+def test_many_macroblocks_add_into_one_sum(codec, oracle):
+    import torch
+    n, w, h, f, gop, merange = 4, 128, 96, 6, 3, 16
+    qs = _few(n)
+    codec.set_quant(_base(n), n)
+    for kind, y in _contents(n, f, h, w)[:2]:
+        bits, sse = codec.probe_gop_rd(torch.from_numpy(y).cuda(), w, h, qs, gop, merange, nframes=f)
+        _check(sse, _truth(oracle, y, n, qs, gop, merange), kind)
+        _check(bits, _bits(oracle, y, n, qs, gop, merange), kind)
+
+
+@pytest.mark.parametrize("w,h", [(32, 32), (48, 48)])
+def test_8x8_pframes_have_no_decode(codec, oracle, w, h):
+    """See the module docstring: no decoder reads an 8x8 P-frame stream, so there is no truth and the
+    probe refuses.  Without P-frames 8x8 is ie_probe_rd."""
+    n, f, gop, merange = 8, 5, 3, 16
+    qs = _candidates(n)
+    codec.set_quant(_base(n), n)
+    y = synth.frames("U", w, h, f, seed=9)
+    for q in qs:
+        enc = np.frombuffer(oracle.encode_video_gop(synth.yuv420(y), w, h, n, q, huffman=False, gop=gop, merange=merange),
+                            dtype=np.uint8).copy()
+        out = np.zeros(f * w * h * 3 // 2, dtype=np.uint8)
+        for mc in (1, 0):
+            r = oracle.lib.ieo_decode_video_gop(oracle._p(enc), enc.size, n, mc, oracle._p(out), out.size,
+                                                C.byref(C.c_int()), C.byref(C.c_int()), C.byref(C.c_int()))
+            assert r < 0, "the oracle decoded an 8x8 P-frame stream: the probe's refusal needs another look"
+    with pytest.raises(IEError) as e:
+        codec.probe_gop_rd(y, w, h, qs, gop, merange, nframes=f)
+    assert e.value.code == IE_EINVAL and "8x8" in str(e.value)
+    for kw in (dict(gop=1, nframes=f), dict(gop=gop, nframes=1)):
+        got = codec.probe_gop_rd(y, w, h, qs, kw["gop"], merange, nframes=kw["nframes"])
+        exp = codec.probe_rd(y, w, h, qs, nframes=kw["nframes"])
+        np.testing.assert_array_equal(got[0], exp[0])
+        np.testing.assert_array_equal(got[1], exp[1])
+    np.testing.assert_array_equal(codec.probe_gop(y, w, h, qs, gop, merange, nframes=f)[:, [1, 2, 4]],
+                                  np.full((len(qs), 3), (w // 16) * (h // 16) * 2 * oracle.bits_needed(merange)))
+    codec.set_quant(_base(4), 4)
+
+
+def test_padded_rows_and_frames_host_and_device(codec, oracle):
+    """64 x 48 x 7, gop 3, stride = w + 13, an odd frame_pitch; host and device y, host and device
+    results, and bits = NULL -- all give the oracle's tables."""
+    import torch
+    n, w, h, f, gop, merange = 4, 64, 48, 7, 3, 16
+    stride, pitch = w + 13, (w + 13) * h + 41
+    assert pitch % 2 == 1
+    qs = _few(n)
+    nq = len(qs)
+    codec.set_quant(_base(n), n)
+    y = synth.frames("shiftB", w, h, f, seed=3)
+    buf = np.full(f * pitch, 0xA5, dtype=np.uint8)
+    for k in range(f):
+        buf[k * pitch: k * pitch + h * stride].reshape(h, stride)[:, :w] = y[k]
+    exp_bits = _bits(oracle, buf, n, qs, gop, merange, stride=stride, frame_pitch=pitch, dims=(f, h, w))
+    exp = _truth(oracle, y, n, qs, gop, merange)
+    dbuf = torch.from_numpy(buf).cuda()
+    lay = dict(nframes=f, stride=stride, frame_pitch=pitch)
+    for src in (buf, dbuf):
+        bits, sse = codec.probe_gop_rd(src, w, h, qs, gop, merange, **lay)
+        _check(sse, exp, "host sse")
+        _check(bits, exp_bits, "host bits")
+        db = torch.full((nq * f,), -1, dtype=torch.int64, device="cuda")
+        ds = torch.full((nq * f,), -1, dtype=torch.int64, device="cuda")
+        pair = (db, ds)
+        assert codec.probe_gop_rd(src, w, h, qs, gop, merange, out=pair, **lay) is pair
+        codec.sync()
+        _check(ds.cpu().numpy().view(np.uint64).reshape(nq, f), exp, "device sse")
+        _check(db.cpu().numpy().view(np.uint64).reshape(nq, f), exp_bits, "device bits")
+        ds.fill_(-1)
+        codec.probe_gop_rd(src, w, h, qs, gop, merange, out=(None, ds), **lay)  # bits = NULL, device
+        codec.sync()
+        _check(ds.cpu().numpy().view(np.uint64).reshape(nq, f), exp, "device sse alone")
+        only = np.zeros((nq, f), dtype=np.uint64)  # bits = NULL, host
+        codec._chk(codec.L.ie_probe_gop_rd(codec.h, src.ctypes.data if src is buf else src.data_ptr(), w, h, stride, pitch, f,
+                                           gop, merange, 1, 1, np.ascontiguousarray(qs).ctypes.data, nq, None,
+                                           only.ctypes.data_as(C.POINTER(C.c_uint64))))
+        _check(only, exp, "host sse alone")
+    _check(codec.probe_gop_rd(buf, w, h, qs, gop, merange, motioncomp=False, **lay)[1],
+           _truth(oracle, y, n, qs, gop, merange, True, False), "no motion compensation")
+
+
+def test_waves_never_change_the_tables(codec, oracle, monkeypatch):
+    """IE_PROBE_GOP_MAX = 1, 3 (chunks of candidates within one group, a partial last chunk), nq and
+    nq + 1 (waves of one group with all candidates); 7 frames at gop 3 end in a group of one I-frame."""
+    n, w, h, f, gop, merange = 4, 32, 32, 7, 3, 16
+    qs = _few(n)
+    nq = len(qs)
+    codec.set_quant(_base(n), n)
+    y = synth.frames("U", w, h, f, seed=17)
+    monkeypatch.delenv("IE_PROBE_GOP_MAX", raising=False)
+    ref = codec.probe_gop_rd(y, w, h, qs, gop, merange, nframes=f)
+    _check(ref[1], _truth(oracle, y, n, qs, gop, merange), "unset sse")
+    _check(ref[0], _bits(oracle, y, n, qs, gop, merange), "unset bits")
+    for cap in (1, 3, nq, nq + 1):
+        monkeypatch.setenv("IE_PROBE_GOP_MAX", str(cap))
+        got = codec.probe_gop_rd(y, w, h, qs, gop, merange, nframes=f)
+        _check(got[0], ref[0], f"bits, IE_PROBE_GOP_MAX={cap}")
+        _check(got[1], ref[1], f"sse, IE_PROBE_GOP_MAX={cap}")
+
+
+def test_rows_equal_the_librarys_own_encodes_and_decodes(codec):
+    n, w, h, f, gop, merange = 4, 64, 48, 7, 3, 16
+    qs = _candidates(n)
+    y = synth.frames("shiftA", w, h, f, seed=11)
+    codec.set_quant(_base(n), n)
+    got = {mc: codec.probe_gop_rd(y, w, h, qs, gop, merange, nframes=f, motioncomp=mc) for mc in (True, False)}
+    for m in (1, 7, len(qs) - 1):
+        codec.set_quant(qs[m], n)
+        for call, mode in ((codec.encode_gop, MODE_FAST), (codec.encode_gop, MODE_EXACT), (codec.encode_gop_groups, MODE_FAST)):
+            out = np.zeros(codec.gop_stream_bound(w, h, f, merange), dtype=np.uint8)
+            fb, end = call(y, w, h, out, gop, merange, nframes=f, mode=mode)
+            for mc in (True, False):
+                np.testing.assert_array_equal(fb, got[mc][0][m], err_msg=f"candidate {m}")
+                dec = np.zeros((f, h, w), dtype=np.uint8)
+                assert codec.decode_gop(out, w, h, dec, gop, merange, f, motioncomp=mc) == end
+                np.testing.assert_array_equal(_sse(dec.astype(np.int64), y), got[mc][1][m], err_msg=f"candidate {m} mc={mc}")
+    codec.set_quant(_base(n), n)
+
+
+def test_arguments(codec, oracle):
+    import torch
+    n, w, h, f, gop, merange = 4, 32, 32, 4, 2, 8
+    y = synth.frames("U", w, h, f, seed=5)
+    codec.set_quant(_base(n), n)
+    q64 = np.stack([scale_matrix(_base(n), 30 + 7 * k) for k in range(64)])
+    exp = _truth(oracle, y, n, q64, gop, merange)
+    _check(codec.probe_gop_rd(y, w, h, q64, gop, merange, nframes=f)[1], exp, "nq = 64")
+    _check(codec.probe_gop_rd(y, w, h, q64[5:6], gop, merange, nframes=f)[1], exp[5:6], "nq = 1")
+    with pytest.raises(IEError) as e:
+        codec.probe_gop_rd(y, w, h, np.concatenate([q64, q64[:1]]), gop, merange, nframes=f)
+    assert e.value.code == IE_EINVAL
+    bad = q64[:4].copy()
+    bad[2, 9] = 0
+    with pytest.raises(IEError) as e:
+        codec.probe_gop_rd(y, w, h, bad, gop, merange, nframes=f)
+    assert e.value.code == IE_EINVAL and "matrix 2" in str(e.value)
+    for bad_range in (-1, 32768):
+        with pytest.raises(IEError) as e:
+            codec.probe_gop_rd(y, w, h, q64[:1], gop, bad_range, nframes=f)
+        assert e.value.code == IE_EINVAL
+    # 48 x 40 with P-frames: ie_probe_gop sizes it, ie_decode_gop refuses it, so does this call
+    z = np.zeros((2, 40, 48), dtype=np.uint8)
+    assert codec.probe_gop(z, 48, 40, q64[:1], 2, merange, nframes=2).shape == (1, 2)
+    with pytest.raises(IEError) as e:
+        codec.probe_gop_rd(z, 48, 40, q64[:1], 2, merange, nframes=2)
+    assert e.value.code == IE_EINVAL and "multiples of 16" in str(e.value)
+    # a host / device mix of the results
+    dev = torch.zeros(f, dtype=torch.int64, device="cuda")
+    host = np.zeros(f, dtype=np.uint64)
+    u64p = C.POINTER(C.c_uint64)
+    for b, s in ((C.cast(C.c_void_p(dev.data_ptr()), u64p), host.ctypes.data_as(u64p)),
+                 (host.ctypes.data_as(u64p), C.cast(C.c_void_p(dev.data_ptr()), u64p))):
+        r = codec.L.ie_probe_gop_rd(codec.h, y.ctypes.data, w, h, w, w * h, f, gop, merange, 1, 1, q64.ctypes.data, 1, b, s)
+        assert r == IE_EINVAL and b"both host or both device" in codec.L.ie_last_error(codec.h)
+    # no P-frame: ie_probe_rd
+    for kw in (dict(gop=1, nframes=f), dict(gop=4, nframes=1)):
+        got = codec.probe_gop_rd(y, w, h, q64[:7], kw["gop"], merange, nframes=kw["nframes"])
+        ref = codec.probe_rd(y, w, h, q64[:7], nframes=kw["nframes"])
+        np.testing.assert_array_equal(got[0], ref[0])
+        np.testing.assert_array_equal(got[1], ref[1])
+
+
+def test_fresh_context_has_no_block_size():
+    from imageencoder_amd import Codec
+    c = Codec(0)
+    try:
+        with pytest.raises(IEError) as e:
+            c.probe_gop_rd(np.zeros((2, 16, 16), dtype=np.uint8), 16, 16, np.ones((1, 16), dtype=np.uint16), 2, 4, nframes=2)
+        assert e.value.code == IE_ENOQUANT
+    finally:
+        c.close()
+
+
+def test_probe_leaves_the_context_untouched(codec):
+    n, w, h, f, gop, merange = 4, 64, 48, 5, 3, 16
+    q = _base(n)
+    y = synth.frames("P", w, h, f, seed=13)
+    codec.set_quant(q, n)
+
+    def state():
+        out = np.zeros(codec.gop_stream_bound(w, h, f, merange), dtype=np.uint8)
+        fb, end = codec.encode_gop(y, w, h, out, gop, merange, nframes=f)
+        table = codec.probe_gop(y, w, h, _few(n), gop, merange, nframes=f)
+        return out.tobytes(), fb.tolist(), end, codec.cos_table().tobytes(), table.tobytes()
+
+    before = state()
+    bits, _ = codec.probe_gop_rd(y, w, h, _candidates(n), gop, merange, nframes=f)
+    after = state()
+    assert before == after
+    assert bits[0].tolist() == before[1]  # candidate 0 is the context's own matrix
