@@ -122,6 +122,13 @@ def load_library(path: str | None = None) -> C.CDLL:
         L.ie_decode_images.restype = C.c_int
         L.ie_decode_images.argtypes = [vp, u8p, C.c_size_t, u64p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                        u8p, C.c_size_t, C.c_size_t, u64p]
+    if hasattr(L, "ie_decode_region"):  # (absent from an older IE_LIB build under comparison)
+        L.ie_decode_region.restype = C.c_int
+        L.ie_decode_region.argtypes = [vp, u8p, C.c_size_t, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_int, C.c_int, u8p, C.c_size_t, C.c_size_t, u64p]
+        L.ie_decode_images_region.restype = C.c_int
+        L.ie_decode_images_region.argtypes = [vp, u8p, C.c_size_t, u64p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_int, C.c_int, C.c_int, u8p, C.c_size_t, C.c_size_t, u64p]
     if hasattr(L, "ie_huffman_decode_batch"):  # (absent from an older IE_LIB build under comparison)
         L.ie_huffman_decode_batch.restype = C.c_int
         L.ie_huffman_decode_batch.argtypes = [vp, u8p, C.c_size_t, u64p, C.c_int, u64p, u16p, u8p, C.c_size_t, u64p]
@@ -212,6 +219,10 @@ def load_host_library(path: str | None = None) -> C.CDLL:
         H.ieh_decode_images.restype = C.c_int64
         H.ieh_decode_images.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_uint64), C.c_int, C.c_int, vp, C.c_size_t,
                                         ip, ip]
+    if hasattr(H, "ieh_decode_image_region"):  # (absent from an older IE_LIB build under comparison)
+        H.ieh_decode_image_region.restype = C.c_int64
+        H.ieh_decode_image_region.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                              C.c_size_t, ip, ip]
     if hasattr(H, "ieh_vdec_open"):  # (absent from an older IE_LIB build under comparison)
         H.ieh_vdec_open.restype = C.c_int
         H.ieh_vdec_open.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, ip, ip, ip, ip, ip,
@@ -812,6 +823,48 @@ class Codec:
                                           eb.ctypes.data_as(u64p)))
         return eb[: nb.size]
 
+    def decode_region(self, stream, w: int, h: int, rect, out=None, start_bit: int = 0, nframes: int = 1,
+                      rle: bool = True, stride: int | None = None, frame_pitch: int | None = None):
+        """Decode only the rectangle ``rect = (x0, y0, rw, rh)`` of ``nframes`` frames of block records
+        (ie_decode_region): row ``r`` of frame ``f`` goes to ``out + f*frame_pitch + r*stride``, ``rw``
+        bytes of it; these pixels equal that crop of what :meth:`decode_frames` writes.  ``out``: a
+        numpy array (host) or torch tensor (device); ``None`` makes a ``(nframes, rh, rw)`` uint8
+        array.  Returns ``(out, end_bit)``: the whole stream is parsed, the end bit is the full
+        decode's."""
+        x0, y0, rw, rh = (int(v) for v in rect)
+        stride = rw if stride is None else stride
+        frame_pitch = stride * rh if frame_pitch is None else frame_pitch
+        if out is None:
+            if stride != rw or frame_pitch != rw * rh:
+                raise IEError(IE_EINVAL, "decode_region: a stride or frame_pitch needs an out buffer")
+            out = np.zeros((nframes, max(rh, 0), max(rw, 0)), dtype=np.uint8)
+        end = C.c_uint64(0)
+        self._chk(self.L.ie_decode_region(self.h, _ptr(stream), _nbytes(stream), start_bit, w, h, nframes, int(rle),
+                                          x0, y0, rw, rh, _ptr(out), stride, frame_pitch, C.byref(end)))
+        return out, int(end.value)
+
+    def decode_images_region(self, streams, in_pitch: int, nbits, w: int, h: int, rect, out=None, start_bit: int = 0,
+                             rle: bool = True, stride: int | None = None, frame_pitch: int | None = None):
+        """The rectangle ``rect = (x0, y0, rw, rh)`` of ``len(nbits)`` independent images in one set
+        of launches (ie_decode_images_region; the arguments of :meth:`decode_images`): image k's
+        region goes to ``out + k*frame_pitch``.  ``out=None`` makes a ``(count, rh, rw)`` uint8
+        array.  Returns ``(out, end_bits)``; raises :class:`IEError` (``IE_EFORMAT``, the message
+        names the image) when an image's stream ends before its last block, wherever that is."""
+        x0, y0, rw, rh = (int(v) for v in rect)
+        stride = rw if stride is None else stride
+        frame_pitch = stride * rh if frame_pitch is None else frame_pitch
+        nb = np.ascontiguousarray(nbits, dtype=np.uint64)
+        if out is None:
+            if stride != rw or frame_pitch != rw * rh:
+                raise IEError(IE_EINVAL, "decode_images_region: a stride or frame_pitch needs an out buffer")
+            out = np.zeros((max(int(nb.size), 1), max(rh, 0), max(rw, 0)), dtype=np.uint8)
+        eb = np.zeros(max(nb.size, 1), dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        self._chk(self.L.ie_decode_images_region(self.h, _ptr(streams), in_pitch, nb.ctypes.data_as(u64p), int(nb.size),
+                                                 start_bit, w, h, int(rle), x0, y0, rw, rh, _ptr(out), stride,
+                                                 frame_pitch, eb.ctypes.data_as(u64p)))
+        return out, eb[: nb.size]
+
     # ---- whole files (libie_host.so, include/ie_host.hpp)
     def _host_chk(self, r: int) -> int:
         if r < 0:
@@ -959,6 +1012,24 @@ class Codec:
         r = self._host_chk(H.ieh_decode_image(self.h, src.ctypes.data, src.size, n, out.ctypes.data, cap, C.byref(w),
                                               C.byref(h)))
         return out[:r].reshape(h.value, w.value)
+
+    def decode_image_file_region(self, file_bytes: bytes, rect, n: int | None = None) -> np.ndarray:
+        """Pixels ``(rh, rw)`` uint8 of the rectangle ``rect = (x0, y0, rw, rh)`` of an encoded image
+        file (ieh_decode_image_region): that crop of what :meth:`decode_image_file` returns.  ``n``:
+        the file's block size (the file does not record it); default: the codec's current one.
+        Raises :class:`IEError` (``IE_EINVAL``) for a rectangle that does not fit the image."""
+        H = load_host_library()
+        n = self.n if n is None else n
+        if n is None:
+            raise IEError(IE_EINVAL, "decode_image_file_region: no block size (pass n or set a matrix)")
+        x0, y0, rw, rh = (int(v) for v in rect)
+        src = np.frombuffer(file_bytes, dtype=np.uint8).copy()
+        w, h = C.c_int(0), C.c_int(0)
+        out = np.zeros(max(rw, 1) * max(rh, 1), dtype=np.uint8)
+        r = self._host_chk(H.ieh_decode_image_region(self.h, src.ctypes.data, src.size, n, x0, y0, rw, rh, out.ctypes.data,
+                                                     out.size, C.byref(w), C.byref(h)))
+        self.n = n  # (the file's matrix is now the context's)
+        return out[:r].reshape(rh, rw)
 
     def decode_image_files(self, files: list[bytes], n: int) -> np.ndarray:
         """Pixels ``(count, h, w)`` uint8 of a batch of encoded image files that share their

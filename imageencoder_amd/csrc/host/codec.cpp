@@ -1023,6 +1023,28 @@ int64_t ieh_decode_image(ie_ctx* c, const uint8_t* enc, size_t len, int n, uint8
     return int64_t(pix.size());
 }
 
+int64_t ieh_decode_image_region(ie_ctx* c, const uint8_t* enc, size_t len, int n, int x0, int y0, int rw, int rh,
+                                uint8_t* out, size_t cap, int* w, int* h) {
+    if (!c || !enc || !out) return IE_EINVAL;
+    dc::StreamHeader sh;
+    std::vector<uint8_t> dec;
+    std::string err;
+    const uint8_t* src = nullptr;
+    size_t srclen = 0;
+    int r = dc::decode_front(c, enc, len, n, false, sh, dec, &src, &srclen, err);
+    if (w) *w = sh.w;
+    if (h) *h = sh.h;
+    if (r) return r;
+    if (x0 < 0 || y0 < 0 || rw < 1 || rh < 1 || int64_t(x0) + rw > sh.w || int64_t(y0) + rh > sh.h)
+        return (ie_set_error(c, "ieh_decode_image_region: the rectangle does not fit the image"), IE_EINVAL);
+    const size_t need = size_t(rw) * size_t(rh);
+    if (need > cap) return IE_ECAP;
+    if ((r = ie_decode_region(c, src, srclen, sh.payload_bit, sh.w, sh.h, 1, sh.rle, x0, y0, rw, rh, out, size_t(rw), need,
+                              nullptr)))
+        return r;
+    return int64_t(need);
+}
+
 int64_t ieh_decode_images(ie_ctx* c, const uint8_t* enc, size_t enc_pitch, const uint64_t* len, int count, int n,
                           uint8_t* out, size_t cap, int* w, int* h) {
     if (!c) return IE_EINVAL;

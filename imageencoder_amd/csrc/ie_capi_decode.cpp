@@ -9,12 +9,10 @@
 
 using namespace iec;
 
-namespace {
-
 // The record stream on the device for the kernels' reads: whole aligned words up to the one holding
 // the last byte, then zeros (16 bytes of padding for the vector loads).  A 16-byte aligned device
 // stream is read in place unless `always`; anything else is copied (device copy or H2D) into buf.
-int stage_stream_in(ie_ctx* c, Buf<uint8_t>& buf, const uint8_t* in, size_t len, bool always, const uint8_t** words) {
+int iec::stage_stream_in(ie_ctx* c, Buf<uint8_t>& buf, const uint8_t* in, size_t len, bool always, const uint8_t** words) {
     const bool in_dev = is_device_ptr(in);
     *words = in;
     if (!always && in_dev && !(reinterpret_cast<uintptr_t>(in) & 15u)) return IE_OK;
@@ -30,7 +28,7 @@ int stage_stream_in(ie_ctx* c, Buf<uint8_t>& buf, const uint8_t* in, size_t len,
 // Where the kernels write pixels: a device destination itself, or buf (grown to span bytes) for a
 // host one -- which copy_frames_out then fills, pixel rows only (the bytes between rows and frames
 // belong to the caller).
-int pixel_dest(ie_ctx* c, Buf<uint8_t>& buf, uint8_t* out, size_t span, bool* out_dev, uint8_t** dpix) {
+int iec::pixel_dest(ie_ctx* c, Buf<uint8_t>& buf, uint8_t* out, size_t span, bool* out_dev, uint8_t** dpix) {
     *out_dev = is_device_ptr(out);
     *dpix = out;
     if (*out_dev) return IE_OK;
@@ -38,6 +36,7 @@ int pixel_dest(ie_ctx* c, Buf<uint8_t>& buf, uint8_t* out, size_t span, bool* ou
     *dpix = buf;
     return r;
 }
+namespace {
 int copy_frames_out(ie_ctx* c, uint8_t* out, const uint8_t* dpix, int f0, int f1, int w, int h, size_t stride,
                     size_t frame_pitch) {
     for (int f = f0; f < f1; f++)
@@ -45,9 +44,10 @@ int copy_frames_out(ie_ctx* c, uint8_t* out, const uint8_t* dpix, int f0, int f1
                               size_t(h), hipMemcpyDeviceToHost));
     return IE_OK;
 }
+}  // namespace
 
 // The decode arguments every path shares; nframes, out, frame_pitch and add_base are the caller's.
-ie::DecArgs dec_args(const ie_ctx* c, int w, int h, int use_rle, size_t stride) {
+ie::DecArgs iec::dec_args(const ie_ctx* c, int w, int h, int use_rle, size_t stride) {
     ie::DecArgs da{};
     da.bx = w / c->n;
     da.by = h / c->n;
@@ -57,6 +57,7 @@ ie::DecArgs dec_args(const ie_ctx* c, int w, int h, int use_rle, size_t stride) 
     return da;
 }
 
+namespace {
 #ifndef IE_GOP_CAPC
 #define IE_GOP_CAPC 1  // 0: (A/B builds) gop decode chunks sized by the I-frame bound alone
 #endif
@@ -141,6 +142,67 @@ int iec::dec_scratch(ie_ctx* c, int n, const RecPlan& pl, size_t batch, ie::RecP
     return IE_OK;
 }
 
+// ie_decode_images' checks of the streams' lengths; *max_bits: the longest.
+int iec::check_image_bits(ie_ctx* c, size_t in_pitch, const uint64_t* nbits, int count, uint64_t start_bit,
+                          uint64_t* max_bits) {
+    *max_bits = 0;
+    for (int k = 0; k < count; k++) {
+        if (nbits[k] / 8 > in_pitch || nbits[k] > uint64_t(in_pitch) * 8)
+            return fail(c, IE_EINVAL, "image " + std::to_string(k) + ": nbits beyond its slot of in_pitch bytes");
+        if (start_bit > nbits[k]) return fail(c, IE_EINVAL, "image " + std::to_string(k) + ": start_bit beyond the stream");
+        *max_bits = std::max(*max_bits, nbits[k]);
+    }
+    return IE_OK;
+}
+
+// Images per sub-batch: what keeps the scratch within 1 GiB, at most IE_DEC_BATCH_MAX, at most count.
+size_t iec::dec_batch_images(int n, const RecPlan& pl, int count) {
+    size_t batch = std::max<size_t>(1, (size_t(1) << 30) / dec_scratch_size(n, pl).img_bytes);
+    if (const char* eb = getenv("IE_DEC_BATCH_MAX"))  // (read on every call: a limit in images, only ever lower)
+        if (atoi(eb) > 0) batch = std::min<size_t>(batch, size_t(atoi(eb)));
+    return std::min<size_t>(batch, size_t(count));
+}
+
+// The batch's stream lengths to d_imgbits and its streams where the kernels read them (*words,
+// slots *pitch bytes apart); h_imgres is grown for the result pairs.
+int iec::stage_image_streams(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64_t* nbits, int count,
+                             uint64_t max_bits, const uint8_t** words_out, size_t* pitch_out) {
+    int r;
+    if ((r = c->d_imgbits.reserve(c, size_t(count)))) return r;
+    if ((r = c->h_imgres.reserve(c, 3 * std::max<size_t>(size_t(count), 16)))) return r;
+    // the stream lengths: through pinned memory into a device array (every workgroup reads its
+    // image's; a read of host memory per workgroup would cost more than the copy)
+    uint64_t* h_bits = c->h_imgres + 2 * size_t(count);
+    std::memcpy(h_bits, nbits, size_t(count) * sizeof(uint64_t));
+    HIPCHK(c, hipMemcpyAsync(c->d_imgbits, h_bits, size_t(count) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    // streams: device slots that are 16-byte aligned, 16-byte pitched are read in place (16-byte
+    // vector loads of whole aligned groups inside [0, nbits[k]), single words up to the one holding
+    // the last bit -- inside the slot, as in_pitch is a multiple of 4 -- and the bits at or past
+    // nbits[k] are cleared by the kernels); anything else is staged into such slots, zero padded
+    const bool in_dev = is_device_ptr(in);
+    const uint8_t* words = in;
+    size_t pitch = in_pitch;
+    if (!in_dev || (reinterpret_cast<uintptr_t>(in) & 15u) || (in_pitch & 15u)) {
+        const size_t max_bytes = size_t((max_bits + 7) / 8);
+        pitch = (max_bytes + 15) / 16 * 16 + 16;
+        if ((r = c->d_dec.reserve(c, pitch * size_t(count)))) return r;
+        HIPCHK(c, hipMemsetAsync(c->d_dec, 0, pitch * size_t(count), c->stream));
+        if (in_dev) {
+            HIPCHK(c, hipMemcpy2DAsync(c->d_dec, pitch, in, in_pitch, std::min(max_bytes, in_pitch), size_t(count),
+                                       hipMemcpyDeviceToDevice, c->stream));
+        } else {
+            for (int k = 0; k < count; k++)
+                if (nbits[k])
+                    HIPCHK(c, hipMemcpyAsync(c->d_dec + size_t(k) * pitch, in + size_t(k) * in_pitch,
+                                             size_t((nbits[k] + 7) / 8), hipMemcpyHostToDevice, c->stream));
+        }
+        words = c->d_dec;
+    }
+    *words_out = words;
+    *pitch_out = pitch;
+    return IE_OK;
+}
+
 namespace {
 
 // Profiling of the single-stream record decode (IE_PROFILE builds, tools/prof_decode.py and
@@ -200,8 +262,6 @@ struct DecProfile {
     int end(ie_ctx*, const ie::RecParseArgs&) { return IE_OK; }
 };
 #endif
-
-constexpr size_t kDecBatchBytes = size_t(1) << 30;    // ie_decode_images: scratch of one sub-batch
 
 }  // namespace
 
@@ -300,7 +360,7 @@ int ie_decode_frames(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bi
 // the launch chain, the synchronisation and the result read are paid once.  One chunk plan for the
 // batch: C from the longest stream, nchunks its chunk count; a shorter stream's trailing chunks
 // hold no record.  Scratch is per image (tables + composites, position lists, walk arrays); a batch
-// whose scratch would pass kDecBatchBytes runs as sub-batches, one after another on the stream,
+// whose scratch would pass 1 GiB (dec_batch_images) runs as sub-batches, one after another on the stream,
 // and the call still waits once.
 int ie_decode_images(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64_t* nbits, int count, uint64_t start_bit,
                      int w, int h, int use_rle, uint8_t* out, size_t stride, size_t frame_pitch, uint64_t* end_bits) {
@@ -308,53 +368,18 @@ int ie_decode_images(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64
     int r = check_frames(c, w, h, count, stride, frame_pitch);
     if (r) return r;
     uint64_t max_bits = 0;
-    for (int k = 0; k < count; k++) {
-        if (nbits[k] / 8 > in_pitch || nbits[k] > uint64_t(in_pitch) * 8)
-            return fail(c, IE_EINVAL, "image " + std::to_string(k) + ": nbits beyond its slot of in_pitch bytes");
-        if (start_bit > nbits[k]) return fail(c, IE_EINVAL, "image " + std::to_string(k) + ": start_bit beyond the stream");
-        max_bits = std::max(max_bits, nbits[k]);
-    }
+    if ((r = check_image_bits(c, in_pitch, nbits, count, start_bit, &max_bits))) return r;
     HIPCHK(c, hipSetDevice(c->device));
     const int n = c->n;
     const uint64_t nblocks = uint64_t(w / n) * (h / n);
     RecPlan pl{};
     if ((r = plan_chunks(c, n, max_bits - start_bit, nblocks, kMaxChunkBits, &pl))) return r;
-    size_t batch = std::max<size_t>(1, kDecBatchBytes / dec_scratch_size(n, pl).img_bytes);
-    if (const char* eb = getenv("IE_DEC_BATCH_MAX"))  // (read on every call: a limit in images, only ever lower)
-        if (atoi(eb) > 0) batch = std::min<size_t>(batch, size_t(atoi(eb)));
-    batch = std::min<size_t>(batch, size_t(count));
+    const size_t batch = dec_batch_images(n, pl, count);
     ie::RecParseArgs pa{};
     if ((r = dec_scratch(c, n, pl, batch, pa))) return r;
-    if ((r = c->d_imgbits.reserve(c, size_t(count)))) return r;
-    if ((r = c->h_imgres.reserve(c, 3 * std::max<size_t>(size_t(count), 16)))) return r;
-    // the stream lengths: through pinned memory into a device array (every workgroup reads its
-    // image's; a read of host memory per workgroup would cost more than the copy)
-    uint64_t* h_bits = c->h_imgres + 2 * size_t(count);
-    std::memcpy(h_bits, nbits, size_t(count) * sizeof(uint64_t));
-    HIPCHK(c, hipMemcpyAsync(c->d_imgbits, h_bits, size_t(count) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    // streams: device slots that are 16-byte aligned, 16-byte pitched are read in place (16-byte
-    // vector loads of whole aligned groups inside [0, nbits[k]), single words up to the one holding
-    // the last bit -- inside the slot, as in_pitch is a multiple of 4 -- and the bits at or past
-    // nbits[k] are cleared by the kernels); anything else is staged into such slots, zero padded
-    const bool in_dev = is_device_ptr(in);
-    const uint8_t* words = in;
-    size_t pitch = in_pitch;
-    if (!in_dev || (reinterpret_cast<uintptr_t>(in) & 15u) || (in_pitch & 15u)) {
-        const size_t max_bytes = size_t((max_bits + 7) / 8);
-        pitch = (max_bytes + 15) / 16 * 16 + 16;
-        if ((r = c->d_dec.reserve(c, pitch * size_t(count)))) return r;
-        HIPCHK(c, hipMemsetAsync(c->d_dec, 0, pitch * size_t(count), c->stream));
-        if (in_dev) {
-            HIPCHK(c, hipMemcpy2DAsync(c->d_dec, pitch, in, in_pitch, std::min(max_bytes, in_pitch), size_t(count),
-                                       hipMemcpyDeviceToDevice, c->stream));
-        } else {
-            for (int k = 0; k < count; k++)
-                if (nbits[k])
-                    HIPCHK(c, hipMemcpyAsync(c->d_dec + size_t(k) * pitch, in + size_t(k) * in_pitch,
-                                             size_t((nbits[k] + 7) / 8), hipMemcpyHostToDevice, c->stream));
-        }
-        words = c->d_dec;
-    }
+    const uint8_t* words;
+    size_t pitch;
+    if ((r = stage_image_streams(c, in, in_pitch, nbits, count, max_bits, &words, &pitch))) return r;
     bool out_dev;
     uint8_t* dpix;
     if ((r = pixel_dest(c, c->d_pix, out, frames_span(count, frame_pitch, stride, w, h), &out_dev, &dpix)))

@@ -216,6 +216,7 @@ struct ie_ctx {
     iec::Buf<uint64_t> d_hufb_res;
     iec::Buf<uint8_t, iec::Mem::Pinned> h_hufb_res;
     iec::Buf<uint8_t> d_pix;
+    iec::Buf<uint8_t> d_region;        // region decodes into host memory: rw*rh pixels per frame, packed
     int last_chunks = 0;               // chunks of the last record decode
     int last_groups = 0;               // and their groups
     int last_spec = 0;                 // 1: the last record decode was the speculative parse
@@ -445,6 +446,17 @@ struct RecPlan {
 // n: the block size of the stream (the context's, or the one a streamed decoder took at open)
 int plan_chunks(ie_ctx* c, int n, uint64_t span, uint64_t nblocks, uint64_t cmax, RecPlan* plan);
 int dec_scratch(ie_ctx* c, int n, const RecPlan& pl, size_t batch, ie::RecParseArgs& a, uint32_t** spec = nullptr);
+// ... and what ie_capi_region.cpp shares with the full decoders: the staging of the record stream
+// (a 16-byte aligned device stream is read in place unless `always`), the pixel destination (a
+// device `out` itself, else buf grown to span bytes), the decode arguments, and the batch call's
+// length checks, sub-batch size and stream staging (ie_decode_images)
+int stage_stream_in(ie_ctx* c, Buf<uint8_t>& buf, const uint8_t* in, size_t len, bool always, const uint8_t** words);
+int pixel_dest(ie_ctx* c, Buf<uint8_t>& buf, uint8_t* out, size_t span, bool* out_dev, uint8_t** dpix);
+ie::DecArgs dec_args(const ie_ctx* c, int w, int h, int use_rle, size_t stride);
+int check_image_bits(ie_ctx* c, size_t in_pitch, const uint64_t* nbits, int count, uint64_t start_bit, uint64_t* max_bits);
+size_t dec_batch_images(int n, const RecPlan& pl, int count);
+int stage_image_streams(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64_t* nbits, int count,
+                        uint64_t max_bits, const uint8_t** words, size_t* pitch);
 
 // ---- ie_capi_stream.cpp: host frames in, host streams out
 // IE_CHUNK_MB's pixel target of a streamed chunk (default 8 MiB; ie_vstream and ie_vdec)

@@ -1,6 +1,6 @@
 // imageencoder_amd/csrc/ie_device.h -- structures shared by the host context (ie_capi.cpp) and
 // the gfx950 kernels (ie_encode.hip, ie_encode4p.hip, ie_huffman.hip, ie_decode.hip,
-// ie_huffman_decode.hip, ie_pframe.hip, ie_probe.hip).
+// ie_decode_region.hip, ie_huffman_decode.hip, ie_pframe.hip, ie_probe.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -308,6 +308,16 @@ int launch_rec_parse_decode(RecParseArgs a, const DecArgs& d, int n, hipStream_t
 // The same five passes over `images` independent streams (the img_ fields set; d.nframes = 1,
 // image y's pixels at d.out + y * d.frame_pitch): every grid gains the image as its y dimension.
 int launch_rec_parse_decode_images(RecParseArgs a, const DecArgs& d, int n, int images, hipStream_t s);
+// The parse passes alone (tables, composition, counts), for a decode pass launched by the caller:
+// fills a.tm, a.hbits and a.levels and returns the levels (< 0: too many chunks).  batch: the
+// kernels' image-batch instantiations over `images` streams (else images is ignored).
+int launch_rec_parse(RecParseArgs& a, int n, int images, bool batch, hipStream_t s);
+// Region decode (ie_decode_region.hip): the same parse, then a decode pass that transforms only the
+// blocks meeting the rectangle (x0, y0, rw, rh) of every frame (image) and stores only its pixels:
+// pixel (x, y) of frame f at d.out + f * d.frame_pitch + (y - y0) * d.stride + (x - x0).  total and
+// end_out are written as by the full decode.  d.add_base is not read.
+int launch_rec_parse_decode_region(const RecParseArgs& a, const DecArgs& d, int n, int images, bool batch, int x0, int y0,
+                                   int rw, int rh, hipStream_t s);
 // the speculative form (a.spec, a.fail set): speculative walks, verifying count pass, decode
 void launch_rec_spec_decode(const RecParseArgs& a, const DecArgs& d, int n, hipStream_t s);
 

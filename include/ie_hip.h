@@ -503,6 +503,40 @@ int ie_decode_images(ie_ctx* ctx, const uint8_t* in, size_t in_pitch, const uint
                      uint64_t start_bit, int w, int h, int use_rle,
                      uint8_t* out, size_t stride, size_t frame_pitch, uint64_t* end_bits);
 
+/* Region decode: only the pixels of the rectangle (x0, y0, rw, rh) -- columns x0 .. x0+rw-1, rows
+ * y0 .. y0+rh-1 -- of every frame (ie_decode_region, the arguments of ie_decode_frames) or of every
+ * image (ie_decode_images_region, the arguments of ie_decode_images; one rectangle for the batch).
+ * `out` receives rw x rh pixels per frame or image: row r of frame f at out + f*frame_pitch +
+ * r*stride, only the rw bytes of a row written, every other byte of `out` left untouched.  These
+ * pixels equal, byte for byte, the same rows and columns of what ie_decode_frames (ie_decode_images)
+ * writes for the same stream and arguments.  in/out: host or device.
+ *  - The whole stream is parsed -- the records are a serial chain -- so *end_bit / end_bits[] are the
+ *    full decode's, and a stream that ends before its last block is IE_EFORMAT with the full decode's
+ *    message (ie_decode_images_region: the lowest such k named, end_bits[k] = UINT64_MAX, every other
+ *    image's region and end bit delivered), also when the missing records lie outside the rectangle.
+ *    What the rectangle saves is the inverse transform of the blocks outside it, the pixel stores
+ *    and, for a host `out`, the copy: rows of rw bytes cross, nothing else.
+ *  - Always the exact parse: ie_set_exact_parse(ctx, 0) does not affect these calls, and
+ *    ie_last_decode_spec returns 0 after them.  ie_last_decode_info reports as for the full call.
+ *  - Checks, in this order: NULL pointers (IE_EINVAL); IE_ENOQUANT and the dimension checks of
+ *    ie_decode_frames on (w, h, nframes or count); the rectangle -- x0 >= 0, y0 >= 0, rw >= 1,
+ *    rh >= 1, x0 + rw <= w, y0 + rh <= h, else IE_EINVAL with a message naming it; stride >= rw, and
+ *    frame_pitch >= (rh-1)*stride + rw when there is more than one frame or image; then the
+ *    start_bit (and nbits) checks of the full call.  Nothing is written after a failed check.
+ *  - A rectangle equal to the whole frame is legal and equals the full decode.
+ *  - One synchronisation per call.  The stream is staged as by the full call (an aligned device
+ *    stream or batch of slots is read in place).  A host `out` is decoded into a packed buffer of
+ *    the context, rw*rh bytes per frame; a device `out` is written in place.
+ *    ie_decode_images_region keeps the 1 GiB sub-batch rule and IE_DEC_BATCH_MAX.
+ *  - I-frames only.  A P-frame's motion vectors reach outside any rectangle, so a region of a gop > 1
+ *    video needs the whole previous frame: decode it with ie_decode_gop / ie_vdec and crop. */
+int ie_decode_region(ie_ctx* ctx, const uint8_t* in, size_t len, uint64_t start_bit, int w, int h,
+                     int nframes, int use_rle, int x0, int y0, int rw, int rh,
+                     uint8_t* out, size_t stride, size_t frame_pitch, uint64_t* end_bit);
+int ie_decode_images_region(ie_ctx* ctx, const uint8_t* in, size_t in_pitch, const uint64_t* nbits, int count,
+                            uint64_t start_bit, int w, int h, int use_rle, int x0, int y0, int rw, int rh,
+                            uint8_t* out, size_t stride, size_t frame_pitch, uint64_t* end_bits);
+
 /* Video payload with P-frames (VideoDecoder.cpp:28-58, Frame.cpp:47-127, Block.cpp:441-496): frame f
  * an I-frame when f % gop == 0 (decoded as ie_decode_frames), otherwise a P-frame: its motion vectors
  * (bits_needed(merange) bits each), the previous decoded frame's blocks at the clamped vectors copied

@@ -415,6 +415,14 @@ int64_t ieh_encode_video_quality(ie_ctx* ctx, const uint8_t* yuv, size_t len, in
 // call with cap = 0 to size the buffer.
 int64_t ieh_decode_image(ie_ctx* ctx, const uint8_t* enc, size_t len, int n, uint8_t* out, size_t cap, int* w,
                          int* h);
+// Decode only the rectangle (x0, y0, rw, rh) of an image file (as ieh_encode_image writes it, with
+// or without the Huffman pass): the front half of ieh_decode_image -- Huffman pass, settings header,
+// ie_set_quant with the header's matrix -- then ie_decode_region.  out (host or device) receives
+// rw*rh bytes, rows packed; they equal that crop of what ieh_decode_image writes.  Returns the
+// bytes written.  *w / *h: the header's size, set whenever the header was read.  A rectangle that
+// does not fit it is IE_EINVAL (nothing is decoded), cap < rw*rh IE_ECAP.
+int64_t ieh_decode_image_region(ie_ctx* ctx, const uint8_t* enc, size_t len, int n, int x0, int y0, int rw, int rh,
+                                uint8_t* out, size_t cap, int* w, int* h);
 /* Decode `count` image files that share their settings (quant matrix, rle, w, h) with block size n:
  * file k is len[k] bytes at enc + k*enc_pitch (host memory); the pixels, w*h bytes per image back to
  * back in file order, go to out (host or device, cap bytes).  Returns the pixel bytes, < 0 on error.
