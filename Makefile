@@ -10,7 +10,7 @@ OBJDIR   := build
 # the FP32 fast path uses explicit fmaf and is unaffected.
 HIPFLAGS := --offload-arch=$(ARCH) -mcode-object-version=5 -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -ffp-contract=off \
             -Wall -Wno-unused-function
-KERNELS  := ie_encode ie_encode4p ie_huffman ie_decode ie_decode_region ie_huffman_decode ie_pframe ie_probe
+KERNELS  := ie_encode ie_encode4p ie_huffman ie_decode ie_decode_region ie_decode_scaled ie_huffman_decode ie_pframe ie_probe
 # the C ABI's host side: every .cpp directly under csrc/ (ie_capi*.cpp, ie_tables.cpp)
 CAPI     := $(basename $(notdir $(wildcard $(CSRC)/*.cpp)))
 OBJS     := $(addprefix $(OBJDIR)/,$(addsuffix .o,$(KERNELS) $(CAPI)))
@@ -62,7 +62,7 @@ ref:
 
 # Check the exact FP64 paths really are unfused: dump the gfx950 ISA of the
 # encode, decode, P-frame and probe kernels and scan it (tools/asmcheck.py; also reports VGPRs / scratch).
-ASMS := $(OBJDIR)/asm/ie_encode.s $(OBJDIR)/asm/ie_encode4p.s $(OBJDIR)/asm/ie_decode.s $(OBJDIR)/asm/ie_decode_region.s $(OBJDIR)/asm/ie_huffman_decode.s $(OBJDIR)/asm/ie_pframe.s $(OBJDIR)/asm/ie_probe.s
+ASMS := $(OBJDIR)/asm/ie_encode.s $(OBJDIR)/asm/ie_encode4p.s $(OBJDIR)/asm/ie_decode.s $(OBJDIR)/asm/ie_decode_region.s $(OBJDIR)/asm/ie_decode_scaled.s $(OBJDIR)/asm/ie_huffman_decode.s $(OBJDIR)/asm/ie_pframe.s $(OBJDIR)/asm/ie_probe.s
 $(OBJDIR)/asm/%.s: $(CSRC)/%.hip $(CSRC)/ie_device.h $(CSRC)/ie_common.hpp $(CSRC)/ie_dct.h $(CSRC)/ie_recbits.h $(CSRC)/ie_encode_blocks.h $(CSRC)/ie_decode_blocks.h $(CSRC)/ie_decode_rec.h
 	@mkdir -p $(OBJDIR)/asm
 	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S $< -o $@

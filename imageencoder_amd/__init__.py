@@ -129,6 +129,13 @@ def load_library(path: str | None = None) -> C.CDLL:
         L.ie_decode_images_region.restype = C.c_int
         L.ie_decode_images_region.argtypes = [vp, u8p, C.c_size_t, u64p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.c_int, C.c_int, u8p, C.c_size_t, C.c_size_t, u64p]
+    if hasattr(L, "ie_decode_scaled"):  # (absent from an older IE_LIB build under comparison)
+        L.ie_decode_scaled.restype = C.c_int
+        L.ie_decode_scaled.argtypes = [vp, u8p, C.c_size_t, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u8p,
+                                       C.c_size_t, C.c_size_t, u64p]
+        L.ie_decode_images_scaled.restype = C.c_int
+        L.ie_decode_images_scaled.argtypes = [vp, u8p, C.c_size_t, u64p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, u8p, C.c_size_t, C.c_size_t, u64p]
     if hasattr(L, "ie_huffman_decode_batch"):  # (absent from an older IE_LIB build under comparison)
         L.ie_huffman_decode_batch.restype = C.c_int
         L.ie_huffman_decode_batch.argtypes = [vp, u8p, C.c_size_t, u64p, C.c_int, u64p, u16p, u8p, C.c_size_t, u64p]
@@ -223,6 +230,9 @@ def load_host_library(path: str | None = None) -> C.CDLL:
         H.ieh_decode_image_region.restype = C.c_int64
         H.ieh_decode_image_region.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
                                               C.c_size_t, ip, ip]
+    if hasattr(H, "ieh_decode_image_scaled"):  # (absent from an older IE_LIB build under comparison)
+        H.ieh_decode_image_scaled.restype = C.c_int64
+        H.ieh_decode_image_scaled.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, ip, ip]
     if hasattr(H, "ieh_vdec_open"):  # (absent from an older IE_LIB build under comparison)
         H.ieh_vdec_open.restype = C.c_int
         H.ieh_vdec_open.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, ip, ip, ip, ip, ip,
@@ -865,6 +875,51 @@ class Codec:
                                                  frame_pitch, eb.ctypes.data_as(u64p)))
         return out, eb[: nb.size]
 
+    def _scaled_out(self, what: str, count: int, w: int, h: int, scale: int, out, stride, frame_pitch):
+        """(out, stride, frame_pitch) of a scaled decode with the defaults filled in: packed rows of
+        ``w // scale`` bytes (a scale the library will refuse sizes ``out`` as scale 1)."""
+        s = scale if isinstance(scale, int) and scale > 0 else 1
+        ow, oh = max(w // s, 0), max(h // s, 0)
+        stride = ow if stride is None else stride
+        frame_pitch = stride * oh if frame_pitch is None else frame_pitch
+        if out is None:
+            if stride != ow or frame_pitch != ow * oh:
+                raise IEError(IE_EINVAL, what + ": a stride or frame_pitch needs an out buffer")
+            out = np.zeros((max(count, 1), oh, ow), dtype=np.uint8)
+        return out, stride, frame_pitch
+
+    def decode_scaled(self, stream, w: int, h: int, scale: int, out=None, start_bit: int = 0, nframes: int = 1,
+                      rle: bool = True, stride: int | None = None, frame_pitch: int | None = None):
+        """Decode ``nframes`` frames of block records at ``1/scale`` of their width and height
+        (ie_decode_scaled; ``scale`` 1, 2, 4 or 8, at most the block size): every output pixel is the
+        mean, rounded half up, of the ``scale x scale`` pixels :meth:`decode_frames` writes there.
+        Row ``r`` of frame ``f`` goes to ``out + f*frame_pitch + r*stride``, ``w // scale`` bytes of
+        it.  ``out``: a numpy array (host) or torch tensor (device); ``None`` makes a
+        ``(nframes, h // scale, w // scale)`` uint8 array.  Returns ``(out, end_bit)``: the whole
+        stream is parsed, the end bit is the full decode's."""
+        out, stride, frame_pitch = self._scaled_out("decode_scaled", nframes, w, h, scale, out, stride, frame_pitch)
+        end = C.c_uint64(0)
+        self._chk(self.L.ie_decode_scaled(self.h, _ptr(stream), _nbytes(stream), start_bit, w, h, nframes, int(rle),
+                                          scale, _ptr(out), stride, frame_pitch, C.byref(end)))
+        return out, int(end.value)
+
+    def decode_images_scaled(self, streams, in_pitch: int, nbits, w: int, h: int, scale: int, out=None, start_bit: int = 0,
+                             rle: bool = True, stride: int | None = None, frame_pitch: int | None = None):
+        """``len(nbits)`` independent images at ``1/scale`` of their size in one set of launches
+        (ie_decode_images_scaled; the arguments of :meth:`decode_images`): image k's picture goes to
+        ``out + k*frame_pitch``.  ``out=None`` makes a ``(count, h // scale, w // scale)`` uint8
+        array.  Returns ``(out, end_bits)``; raises :class:`IEError` (``IE_EFORMAT``, the message
+        names the image) when an image's stream ends before its last block."""
+        nb = np.ascontiguousarray(nbits, dtype=np.uint64)
+        out, stride, frame_pitch = self._scaled_out("decode_images_scaled", int(nb.size), w, h, scale, out, stride,
+                                                    frame_pitch)
+        eb = np.zeros(max(nb.size, 1), dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        self._chk(self.L.ie_decode_images_scaled(self.h, _ptr(streams), in_pitch, nb.ctypes.data_as(u64p), int(nb.size),
+                                                 start_bit, w, h, int(rle), scale, _ptr(out), stride, frame_pitch,
+                                                 eb.ctypes.data_as(u64p)))
+        return out, eb[: nb.size]
+
     # ---- whole files (libie_host.so, include/ie_host.hpp)
     def _host_chk(self, r: int) -> int:
         if r < 0:
@@ -1030,6 +1085,29 @@ class Codec:
                                                      out.size, C.byref(w), C.byref(h)))
         self.n = n  # (the file's matrix is now the context's)
         return out[:r].reshape(rh, rw)
+
+    def decode_image_file_scaled(self, file_bytes: bytes, scale: int, n: int | None = None) -> np.ndarray:
+        """Pixels ``(h // scale, w // scale)`` uint8 of an encoded image file at ``1/scale`` of its
+        size (ieh_decode_image_scaled): the rounded box means of what :meth:`decode_image_file`
+        returns.  ``n``: the file's block size (the file does not record it); default: the codec's
+        current one.  Raises :class:`IEError` (``IE_EINVAL``) for a scale that is not 1, 2, 4 or 8 or
+        exceeds ``n``."""
+        H = load_host_library()
+        n = self.n if n is None else n
+        if n is None:
+            raise IEError(IE_EINVAL, "decode_image_file_scaled: no block size (pass n or set a matrix)")
+        src = np.frombuffer(file_bytes, dtype=np.uint8).copy()
+        w, h = C.c_int(0), C.c_int(0)
+        # (the header gives the size: cap = 0 sizes the buffer, as for ieh_decode_image)
+        r = H.ieh_decode_image_scaled(self.h, src.ctypes.data, src.size, n, scale, src.ctypes.data, 0, C.byref(w), C.byref(h))
+        if r != IE_ECAP:
+            self._host_chk(r)
+        ow, oh = w.value // scale, h.value // scale
+        out = np.zeros(ow * oh, dtype=np.uint8)
+        r = self._host_chk(H.ieh_decode_image_scaled(self.h, src.ctypes.data, src.size, n, scale, out.ctypes.data, out.size,
+                                                     C.byref(w), C.byref(h)))
+        self.n = n  # (the file's matrix is now the context's)
+        return out[:r].reshape(oh, ow)
 
     def decode_image_files(self, files: list[bytes], n: int) -> np.ndarray:
         """Pixels ``(count, h, w)`` uint8 of a batch of encoded image files that share their

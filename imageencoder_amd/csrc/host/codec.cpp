@@ -1045,6 +1045,26 @@ int64_t ieh_decode_image_region(ie_ctx* c, const uint8_t* enc, size_t len, int n
     return int64_t(need);
 }
 
+int64_t ieh_decode_image_scaled(ie_ctx* c, const uint8_t* enc, size_t len, int n, int scale, uint8_t* out, size_t cap, int* w,
+                                int* h) {
+    if (!c || !enc || !out) return IE_EINVAL;
+    dc::StreamHeader sh;
+    std::vector<uint8_t> dec;
+    std::string err;
+    const uint8_t* src = nullptr;
+    size_t srclen = 0;
+    int r = dc::decode_front(c, enc, len, n, false, sh, dec, &src, &srclen, err);
+    if (w) *w = sh.w;
+    if (h) *h = sh.h;
+    if (r) return r;
+    if (scale < 1 || scale > n || (scale & (scale - 1)))
+        return (ie_set_error(c, "ieh_decode_image_scaled: the scale is not a power of two from 1 to the block size"), IE_EINVAL);
+    const size_t ow = size_t(sh.w / scale), need = ow * size_t(sh.h / scale);
+    if (need > cap) return IE_ECAP;
+    if ((r = ie_decode_scaled(c, src, srclen, sh.payload_bit, sh.w, sh.h, 1, sh.rle, scale, out, ow, need, nullptr))) return r;
+    return int64_t(need);
+}
+
 int64_t ieh_decode_images(ie_ctx* c, const uint8_t* enc, size_t enc_pitch, const uint64_t* len, int count, int n,
                           uint8_t* out, size_t cap, int* w, int* h) {
     if (!c) return IE_EINVAL;

@@ -1,7 +1,10 @@
 // imageencoder_amd/csrc/ie_capi_region.cpp -- region decode of the C ABI: ie_decode_region and
 // ie_decode_images_region.  The whole stream is parsed (chunk plan, scratch and stream staging are
 // the full decoders', ie_capi_decode.cpp); only the blocks meeting the rectangle are transformed and
-// only the rectangle's pixels are stored and, for a host destination, copied out.
+// only the rectangle's pixels are stored and, for a host destination, copied out.  The calls' bodies
+// behind their checks -- decode_part and decode_images_part: the parse, a decode pass that writes
+// part of every frame, the packed buffer and row copies of a host destination -- are shared with
+// the scaled decode (ie_capi_scaled.cpp) through ie_ctx.hpp.
 #include "ie_ctx.hpp"
 
 using namespace iec;
@@ -49,17 +52,14 @@ int copy_region_out(ie_ctx* c, uint8_t* out, const RegionDest& d, int f, int rw,
 
 }  // namespace
 
-extern "C" {
-
-int ie_decode_region(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bit, int w, int h, int nframes, int use_rle,
-                     int x0, int y0, int rw, int rh, uint8_t* out, size_t stride, size_t frame_pitch, uint64_t* end_bit) {
-    if (!c || !in || !out) return IE_EINVAL;
-    int r = check_region(c, w, h, nframes, x0, y0, rw, rh, stride, frame_pitch);
-    if (r) return r;
+int iec::decode_part(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bit, int w, int h, int nframes, int use_rle,
+                     int rw, int rh, uint8_t* out, size_t stride, size_t frame_pitch, uint64_t* end_bit,
+                     const PartLaunch& launch) {
     if (start_bit > uint64_t(len) * 8) return fail(c, IE_EINVAL, "start_bit beyond the stream");
     HIPCHK(c, hipSetDevice(c->device));
     const int n = c->n;
     const uint8_t* words;
+    int r;
     if ((r = stage_stream_in(c, c->d_dec, in, len, false, &words))) return r;
     const uint64_t nbits = uint64_t(len) * 8;
     const uint64_t nblocks = uint64_t(nframes) * (w / n) * (h / n);
@@ -82,8 +82,8 @@ int ie_decode_region(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bi
     pa.end_out = c->h_decres.dev();
     // (as in ie_decode_frames the result words need no clearing: the last chunk's wave always writes
     // the record total, and the end bit is read only when that total covers the last block, whose
-    // lane writes it whether or not the block meets the rectangle)
-    const int levels = ie::launch_rec_parse_decode_region(pa, da, n, 1, false, x0, y0, rw, rh, c->stream);
+    // lane writes it whatever part of the block is stored)
+    const int levels = launch(pa, da, n, 1, false, c->stream);
     if (levels < 0) return fail(c, IE_EINVAL, "stream too long for one decode call");
     HIPCHK(c, hipGetLastError());
     c->last_chunks = pa.nchunks;
@@ -99,13 +99,11 @@ int ie_decode_region(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bi
     return IE_OK;
 }
 
-int ie_decode_images_region(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64_t* nbits, int count,
-                            uint64_t start_bit, int w, int h, int use_rle, int x0, int y0, int rw, int rh, uint8_t* out,
-                            size_t stride, size_t frame_pitch, uint64_t* end_bits) {
-    if (!c || !in || !nbits || !out) return IE_EINVAL;
-    int r = check_region(c, w, h, count, x0, y0, rw, rh, stride, frame_pitch);
-    if (r) return r;
+int iec::decode_images_part(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64_t* nbits, int count,
+                            uint64_t start_bit, int w, int h, int use_rle, int rw, int rh, uint8_t* out, size_t stride,
+                            size_t frame_pitch, uint64_t* end_bits, const PartLaunch& launch) {
     uint64_t max_bits = 0;
+    int r;
     if ((r = check_image_bits(c, in_pitch, nbits, count, start_bit, &max_bits))) return r;
     HIPCHK(c, hipSetDevice(c->device));
     const int n = c->n;
@@ -134,7 +132,7 @@ int ie_decode_images_region(ie_ctx* c, const uint8_t* in, size_t in_pitch, const
         pa.end_out = c->h_imgres.dev() + 2 * k0;
         pa.total = c->h_imgres.dev() + 2 * k0 + 1;
         da.out = rd.dpix + k0 * rd.frame_pitch;
-        levels = ie::launch_rec_parse_decode_region(pa, da, n, m, true, x0, y0, rw, rh, c->stream);
+        levels = launch(pa, da, n, m, true, c->stream);
         if (levels < 0) return fail(c, IE_EINVAL, "stream too long for one decode call");
         HIPCHK(c, hipGetLastError());
     }
@@ -152,6 +150,32 @@ int ie_decode_images_region(ie_ctx* c, const uint8_t* in, size_t in_pitch, const
     }
     if (bad >= 0) return fail(c, IE_EFORMAT, "image " + std::to_string(bad) + ": stream ends before the last block");
     return IE_OK;
+}
+
+extern "C" {
+
+int ie_decode_region(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bit, int w, int h, int nframes, int use_rle,
+                     int x0, int y0, int rw, int rh, uint8_t* out, size_t stride, size_t frame_pitch, uint64_t* end_bit) {
+    if (!c || !in || !out) return IE_EINVAL;
+    int r = check_region(c, w, h, nframes, x0, y0, rw, rh, stride, frame_pitch);
+    if (r) return r;
+    return decode_part(c, in, len, start_bit, w, h, nframes, use_rle, rw, rh, out, stride, frame_pitch, end_bit,
+                       [=](const ie::RecParseArgs& pa, const ie::DecArgs& da, int n, int images, bool batch, hipStream_t s) {
+                           return ie::launch_rec_parse_decode_region(pa, da, n, images, batch, x0, y0, rw, rh, s);
+                       });
+}
+
+int ie_decode_images_region(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64_t* nbits, int count,
+                            uint64_t start_bit, int w, int h, int use_rle, int x0, int y0, int rw, int rh, uint8_t* out,
+                            size_t stride, size_t frame_pitch, uint64_t* end_bits) {
+    if (!c || !in || !nbits || !out) return IE_EINVAL;
+    int r = check_region(c, w, h, count, x0, y0, rw, rh, stride, frame_pitch);
+    if (r) return r;
+    return decode_images_part(c, in, in_pitch, nbits, count, start_bit, w, h, use_rle, rw, rh, out, stride, frame_pitch,
+                              end_bits,
+                              [=](const ie::RecParseArgs& pa, const ie::DecArgs& da, int n, int images, bool batch, hipStream_t s) {
+                                  return ie::launch_rec_parse_decode_region(pa, da, n, images, batch, x0, y0, rw, rh, s);
+                              });
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -216,7 +217,7 @@ struct ie_ctx {
     iec::Buf<uint64_t> d_hufb_res;
     iec::Buf<uint8_t, iec::Mem::Pinned> h_hufb_res;
     iec::Buf<uint8_t> d_pix;
-    iec::Buf<uint8_t> d_region;        // region decodes into host memory: rw*rh pixels per frame, packed
+    iec::Buf<uint8_t> d_region;        // region and scaled decodes into host memory: rw*rh pixels per frame, packed
     int last_chunks = 0;               // chunks of the last record decode
     int last_groups = 0;               // and their groups
     int last_spec = 0;                 // 1: the last record decode was the speculative parse
@@ -457,6 +458,21 @@ int check_image_bits(ie_ctx* c, size_t in_pitch, const uint64_t* nbits, int coun
 size_t dec_batch_images(int n, const RecPlan& pl, int count);
 int stage_image_streams(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64_t* nbits, int count,
                         uint64_t max_bits, const uint8_t** words, size_t* pitch);
+
+// ---- ie_capi_region.cpp: decodes that write part of every frame (region and scaled decode)
+// The decode pass such a call launches after the parse: (parse arguments, decode arguments with the
+// destination set, block size, images, batch, stream) -> composition levels, < 0 on failure.
+using PartLaunch = std::function<int(const ie::RecParseArgs&, const ie::DecArgs&, int, int, bool, hipStream_t)>;
+// The body of a call that decodes rw x rh pixels per frame of a stream of w x h frames, behind its
+// checks of the dimensions and the destination: the start_bit check of ie_decode_frames, stream
+// staging, chunk plan, `launch`, one synchronisation, IE_EFORMAT as the full decode, and for a host
+// `out` the packed buffer d_region and the copy of its rows of rw bytes.
+int decode_part(ie_ctx* c, const uint8_t* in, size_t len, uint64_t start_bit, int w, int h, int nframes, int use_rle, int rw,
+                int rh, uint8_t* out, size_t stride, size_t frame_pitch, uint64_t* end_bit, const PartLaunch& launch);
+// The same for a batch of images (ie_decode_images' nbits checks, sub-batches and per-image errors).
+int decode_images_part(ie_ctx* c, const uint8_t* in, size_t in_pitch, const uint64_t* nbits, int count, uint64_t start_bit,
+                       int w, int h, int use_rle, int rw, int rh, uint8_t* out, size_t stride, size_t frame_pitch,
+                       uint64_t* end_bits, const PartLaunch& launch);
 
 // ---- ie_capi_stream.cpp: host frames in, host streams out
 // IE_CHUNK_MB's pixel target of a streamed chunk (default 8 MiB; ie_vstream and ie_vdec)

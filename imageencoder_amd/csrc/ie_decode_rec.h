@@ -1,7 +1,8 @@
-// imageencoder_amd/csrc/ie_decode_rec.h -- what the record decode passes of ie_decode.hip and the
-// region decode pass of ie_decode_region.hip share: bit reads from a wave's LDS copy of the stream,
-// record lengths, the zig-zag ranks, a chunk's entry offset, the launch's record span, the image
-// batch's argument rebasing and the staging of stream words into LDS.
+// imageencoder_amd/csrc/ie_decode_rec.h -- what the record decode passes of ie_decode.hip, the
+// region decode pass of ie_decode_region.hip and the scaled decode pass of ie_decode_scaled.hip
+// share: bit reads from a wave's LDS copy of the stream, record lengths, the zig-zag ranks, a
+// chunk's entry offset, the launch's record span, the image batch's argument rebasing and the
+// staging of stream words into LDS.
 #pragma once
 #include "ie_decode_blocks.h"
 

@@ -1,6 +1,6 @@
 // imageencoder_amd/csrc/ie_device.h -- structures shared by the host context (ie_capi.cpp) and
 // the gfx950 kernels (ie_encode.hip, ie_encode4p.hip, ie_huffman.hip, ie_decode.hip,
-// ie_decode_region.hip, ie_huffman_decode.hip, ie_pframe.hip, ie_probe.hip).
+// ie_decode_region.hip, ie_decode_scaled.hip, ie_huffman_decode.hip, ie_pframe.hip, ie_probe.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -318,6 +318,13 @@ int launch_rec_parse(RecParseArgs& a, int n, int images, bool batch, hipStream_t
 // end_out are written as by the full decode.  d.add_base is not read.
 int launch_rec_parse_decode_region(const RecParseArgs& a, const DecArgs& d, int n, int images, bool batch, int x0, int y0,
                                    int rw, int rh, hipStream_t s);
+// Scaled decode (ie_decode_scaled.hip): the same parse, then a decode pass that transforms every
+// block, takes the rounded integer mean of its pixels over scale x scale cells (scale = 1, 2, 4 or 8,
+// at most n) and stores the (n/scale)^2 means: pixel (X, Y) of frame f's bx*n/scale x by*n/scale
+// picture at d.out + f * d.frame_pitch + Y * d.stride + X.  total and end_out are written as by the
+// full decode.  d.add_base is not read.  < -1: no such scale.
+int launch_rec_parse_decode_scaled(const RecParseArgs& a, const DecArgs& d, int n, int images, bool batch, int scale,
+                                   hipStream_t s);
 // the speculative form (a.spec, a.fail set): speculative walks, verifying count pass, decode
 void launch_rec_spec_decode(const RecParseArgs& a, const DecArgs& d, int n, hipStream_t s);
 

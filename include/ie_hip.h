@@ -537,6 +537,43 @@ int ie_decode_images_region(ie_ctx* ctx, const uint8_t* in, size_t in_pitch, con
                             uint64_t start_bit, int w, int h, int use_rle, int x0, int y0, int rw, int rh,
                             uint8_t* out, size_t stride, size_t frame_pitch, uint64_t* end_bits);
 
+/* Scaled decode: every frame (ie_decode_scaled, the arguments of ie_decode_frames) or image
+ * (ie_decode_images_scaled, the arguments of ie_decode_images) at 1/scale of its width and height:
+ * the thumbnail out of the decode pass.  scale = s must be a power of two with 1 <= s <= N, N the
+ * context's block size: 1, 2, 4 for 4x4 blocks and 1, 2, 4, 8 for 8x8.  `out` receives ow x oh
+ * pixels per frame or image, ow = w/s, oh = h/s (exact: w and h are multiples of N): row r of frame
+ * f at out + f*frame_pitch + r*stride, only the ow bytes of a row written, every other byte of `out`
+ * left untouched.  in/out: host or device.
+ *  - The pixel, exactly.  With `full` what ie_decode_frames (ie_decode_images) writes for the same
+ *    stream and arguments,
+ *      out[f][Y][X] = (sum over dy < s, dx < s of full[f][Y*s+dy][X*s+dx] + s*s/2) >> (2*log2 s):
+ *    the box mean of the decoded integer pixels -- after +128, clamp and truncation -- rounded half
+ *    up.  Nothing about the transform is approximated; the mean is not formed from the DC value or
+ *    from the unclamped doubles.  scale = 1 equals the full decode byte for byte.
+ *  - The whole stream is parsed, so *end_bit / end_bits[] are the full decode's, and a stream that
+ *    ends before its last block is IE_EFORMAT with the full decode's message (ie_decode_images_scaled:
+ *    the lowest such k named, end_bits[k] = UINT64_MAX, every other image delivered).  A host `out`
+ *    receives nothing from an ie_decode_scaled call that returns IE_EFORMAT.  Every block is
+ *    transformed; what a scale saves is stores and, for a host `out`, the copy: 1/s^2 of the bytes.
+ *  - Always the exact parse: ie_set_exact_parse(ctx, 0) does not affect these calls, and
+ *    ie_last_decode_spec returns 0 after them.  ie_last_decode_info reports as for the full call.
+ *  - Checks, in this order: NULL pointers (IE_EINVAL); IE_ENOQUANT and the dimension checks of
+ *    ie_decode_frames on (w, h, nframes or count); the scale, else IE_EINVAL with a message naming
+ *    the scale; stride >= ow, and frame_pitch >= (oh-1)*stride + ow when there is more than one
+ *    frame or image; then the start_bit (and nbits) checks of the full call.  Nothing is written
+ *    after a failed check.
+ *  - One synchronisation per call.  The stream is staged as by the full call (an aligned device
+ *    stream or batch of slots is read in place).  A host `out` is decoded into a packed buffer of
+ *    the context, ow*oh bytes per frame, and copied as rows of ow bytes; a device `out` is written
+ *    in place.  ie_decode_images_scaled keeps the 1 GiB sub-batch rule and IE_DEC_BATCH_MAX.
+ *  - I-frames only, as the region calls: a P-frame needs the whole previous frame at full size. */
+int ie_decode_scaled(ie_ctx* ctx, const uint8_t* in, size_t len, uint64_t start_bit, int w, int h,
+                     int nframes, int use_rle, int scale,
+                     uint8_t* out, size_t stride, size_t frame_pitch, uint64_t* end_bit);
+int ie_decode_images_scaled(ie_ctx* ctx, const uint8_t* in, size_t in_pitch, const uint64_t* nbits, int count,
+                            uint64_t start_bit, int w, int h, int use_rle, int scale,
+                            uint8_t* out, size_t stride, size_t frame_pitch, uint64_t* end_bits);
+
 /* Video payload with P-frames (VideoDecoder.cpp:28-58, Frame.cpp:47-127, Block.cpp:441-496): frame f
  * an I-frame when f % gop == 0 (decoded as ie_decode_frames), otherwise a P-frame: its motion vectors
  * (bits_needed(merange) bits each), the previous decoded frame's blocks at the clamped vectors copied

@@ -423,6 +423,13 @@ int64_t ieh_decode_image(ie_ctx* ctx, const uint8_t* enc, size_t len, int n, uin
 // does not fit it is IE_EINVAL (nothing is decoded), cap < rw*rh IE_ECAP.
 int64_t ieh_decode_image_region(ie_ctx* ctx, const uint8_t* enc, size_t len, int n, int x0, int y0, int rw, int rh,
                                 uint8_t* out, size_t cap, int* w, int* h);
+// Decode an image file at 1/scale of its width and height (scale = 1, 2, 4 or 8, at most n): the
+// front half of ieh_decode_image_region, then ie_decode_scaled.  out (host or device) receives
+// ow*oh bytes, ow = w/scale, oh = h/scale, rows packed: the rounded box means of what
+// ieh_decode_image writes.  Returns the bytes written.  *w / *h: the header's full size, set
+// whenever the header was read.  A bad scale is IE_EINVAL (nothing is decoded), cap < ow*oh IE_ECAP.
+int64_t ieh_decode_image_scaled(ie_ctx* ctx, const uint8_t* enc, size_t len, int n, int scale, uint8_t* out, size_t cap,
+                                int* w, int* h);
 /* Decode `count` image files that share their settings (quant matrix, rle, w, h) with block size n:
  * file k is len[k] bytes at enc + k*enc_pitch (host memory); the pixels, w*h bytes per image back to
  * back in file order, go to out (host or device, cap bytes).  Returns the pixel bytes, < 0 on error.

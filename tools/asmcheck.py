@@ -130,6 +130,14 @@ BUDGETS = {
     "_ZN2ie15encode4p_kernelILb0ELb1EEEvNS_7EncArgsEPKNS_9EncTablesE": (6, 0),
     "_ZN2ie15encode4p_kernelILb1ELb1EEEvNS_7EncArgsEPKNS_9EncTablesE": (6, 0),
 }
+# the scaled decode pass (ie_decode_scaled.hip): no scratch in any instantiation, and the 8x8 ones
+# at rec_decode_kernel<8>'s three waves per SIMD
+BUDGETS.update({
+    f"_ZN2ie17rec_scaled_kernelILi{n}ELi{s}ELb{b}EEEvNS_12RecParseArgsENS_7DecArgsE": (6 if n == 4 else 3, 0)
+    for n in (4, 8) for s in (1, 2, 4, 8) if s <= n for b in (0, 1)
+})
+
+
 def main(paths):
     rc = 0
     srcs = [a for a in paths if a.endswith((".hip", ".h", ".hpp", ".cpp"))]
