@@ -282,6 +282,12 @@ def _nbytes(a) -> int:
     return a.numel() * a.element_size()
 
 
+def _pitches(w: int, h: int, stride, frame_pitch):
+    """(stride, frame_pitch) with the defaults of packed rows and packed frames."""
+    stride = w if stride is None else stride
+    return stride, stride * h if frame_pitch is None else frame_pitch
+
+
 def write_header(n: int, q, rle: bool, w: int, h: int, huffman: bool = False, video: bool = False,
                  frames: int = 0, gop: int = 1, merange: int = 0):
     """Settings header bytes + bit length (host library; ImageEncoder.cpp:84-94, VideoEncoder.cpp:60-73)."""
@@ -366,8 +372,7 @@ class VideoStream:
     def __init__(self, codec, w, h, head, start_bit, max_frames, stride, frame_pitch, rle, mode, gop=1, merange=0):
         self.c = codec
         self.w, self.h = w, h
-        self.stride = w if stride is None else stride
-        self.frame_pitch = self.stride * h if frame_pitch is None else frame_pitch
+        self.stride, self.frame_pitch = _pitches(w, h, stride, frame_pitch)
         head = np.zeros(1, dtype=np.uint8) if head is None else np.ascontiguousarray(head, dtype=np.uint8)
         self._head = head
         v = C.c_void_p()
@@ -433,8 +438,7 @@ class VideoDecodeStream:
         """Up to ``max_frames`` frames into ``out`` (host or device; frame i of the call at
         ``i * frame_pitch``); returns how many, 0 after the last.  A stream that ends early raises
         :class:`IEError` (IE_EFORMAT) whose ``got`` is the number of whole frames written first."""
-        stride = self.w if stride is None else stride
-        frame_pitch = stride * self.h if frame_pitch is None else frame_pitch
+        stride, frame_pitch = _pitches(self.w, self.h, stride, frame_pitch)
         got = C.c_int(0)
         r = self.c.L.ie_vdec_next(self.v, _ptr(out), stride, frame_pitch, max_frames, C.byref(got))
         if r != IE_OK:
@@ -532,8 +536,7 @@ class Codec:
         """Append the block records of ``nframes`` frames to ``out`` from ``start_bit``.
         ``y``/``out``: numpy arrays (host) or torch tensors (device).  Returns
         ``(frame_bits, end_bit)`` or ``None`` when ``want_sizes`` is False (async)."""
-        stride = w if stride is None else stride
-        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        stride, frame_pitch = _pitches(w, h, stride, frame_pitch)
         fb = np.zeros(nframes, dtype=np.uint64)
         end = C.c_uint64(0)
         fbp = fb.ctypes.data_as(C.POINTER(C.c_uint64)) if want_sizes else None
@@ -565,8 +568,7 @@ class Codec:
                                 frame_pitch, nframes, rle, mode)
 
     def _encode_gop(self, call, y, w, h, out, gop, merange, start_bit, stride, frame_pitch, nframes, rle, mode):
-        stride = w if stride is None else stride
-        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        stride, frame_pitch = _pitches(w, h, stride, frame_pitch)
         fb = np.zeros(nframes, dtype=np.uint64)
         end = C.c_uint64(0)
         self._chk(call(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, gop, merange, int(rle), mode, _ptr(out),
@@ -577,8 +579,7 @@ class Codec:
                    length: int | None = None, stride: int | None = None, frame_pitch: int | None = None,
                    rle: bool = True, motioncomp: bool = True) -> int:
         """Decode an I/P-frame payload (VideoDecoder / Frame::loadFromStream) into ``out``; the end bit."""
-        stride = w if stride is None else stride
-        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        stride, frame_pitch = _pitches(w, h, stride, frame_pitch)
         end = C.c_uint64(0)
         self._chk(self.L.ie_decode_gop(self.h, _ptr(stream), _nbytes(stream) if length is None else length, start_bit,
                                        w, h, nframes, gop, merange, int(rle), int(motioncomp), _ptr(out), stride,
@@ -591,8 +592,7 @@ class Codec:
         """count_bytes (device ``out``): also count every image's stream bytes for the following
         Huffman pass (:meth:`huffman_begin_after_encode` then skips its histogram kernel);
         implies want_sizes=False."""
-        stride = w if stride is None else stride
-        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        stride, frame_pitch = _pitches(w, h, stride, frame_pitch)
         if count_bytes:
             self._chk(self.L.ie_encode_images_counted(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, int(rle),
                                                       mode, _ptr(out), out_pitch, start_bit))
@@ -606,8 +606,7 @@ class Codec:
     def quantize_frames(self, y, w: int, h: int, nframes: int = 1, stride: int | None = None,
                         frame_pitch: int | None = None, mode: int = MODE_FAST) -> np.ndarray:
         """Quantised coefficients (natural order) of every block: shape (blocks, n*n) int16."""
-        stride = w if stride is None else stride
-        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        stride, frame_pitch = _pitches(w, h, stride, frame_pitch)
         n = self.n
         coef = np.zeros((nframes * (w // n) * (h // n), n * n), dtype=np.int16)
         self._chk(self.L.ie_quantize_frames(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, mode,
@@ -622,23 +621,34 @@ class Codec:
         after ``set_quant(qs[m])``.  The codec's own matrix is left as it was.  ``y``: numpy array
         or torch tensor.  ``out``: an optional device tensor of ``nq * nframes`` 64-bit entries,
         which receives the sums instead -- the call is then asynchronous and returns ``out``."""
-        stride = w if stride is None else stride
-        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        return self._probe("probe_sizes", False, y, w, h, qs, nframes, (int(rle),), stride, frame_pitch, out)
+
+    def _probe(self, name, rd, y, w, h, qs, nframes, ints, stride, frame_pitch, out):
+        """The body of the four probes.  ``name``: the method, whose entry point is ``ie_<name>``;
+        ``ints``: that call's integer arguments between ``nframes`` and the candidates; ``rd``: the
+        results are the pair ``(bits, sse)``, not ``bits`` alone."""
+        stride, frame_pitch = _pitches(w, h, stride, frame_pitch)
         nn = (self.n or 0) ** 2
         qs = np.ascontiguousarray(np.asarray(qs, dtype=np.uint16).reshape(-1, nn) if nn else
                                   np.asarray(qs, dtype=np.uint16))
         nq = qs.shape[0] if nn else 1
         u64p = C.POINTER(C.c_uint64)
         if out is not None:
-            if _nbytes(out) < 8 * nq * nframes:
-                raise IEError(IE_EINVAL, "probe_sizes: out holds fewer than nq * nframes 64-bit entries")
-            self._chk(self.L.ie_probe_sizes(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, int(rle),
-                                            qs.ctypes.data, nq, C.cast(C.c_void_p(_ptr(out)), u64p)))
+            res = (out,)
+            if rd:
+                dbits, dsse = out
+                res = (dbits, dsse)
+            if any(t is not None and _nbytes(t) < 8 * nq * nframes for t in res):
+                raise IEError(IE_EINVAL, f"{name}: out holds fewer than nq * nframes 64-bit entries")
+            ptrs = [None if t is None else C.cast(C.c_void_p(_ptr(t)), u64p) for t in res]
+        else:
+            res = tuple(np.zeros((max(nq, 1), nframes), dtype=np.uint64) for _ in range(2 if rd else 1))
+            ptrs = [t.ctypes.data_as(u64p) for t in res]
+        self._chk(getattr(self.L, "ie_" + name)(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, *ints,
+                                                qs.ctypes.data, nq, *ptrs))
+        if out is not None:
             return out
-        bits = np.zeros((max(nq, 1), nframes), dtype=np.uint64)
-        self._chk(self.L.ie_probe_sizes(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, int(rle), qs.ctypes.data,
-                                        nq, bits.ctypes.data_as(u64p)))
-        return bits
+        return res if rd else res[0]
 
     def probe_gop(self, y, w: int, h: int, qs, gop: int, merange: int, nframes: int = 1, rle: bool = True,
                   stride: int | None = None, frame_pitch: int | None = None, out=None) -> np.ndarray:
@@ -647,23 +657,7 @@ class Codec:
         and ``merange`` after ``set_quant(qs[m])``.  The codec's own matrix is left as it was.
         ``out``: an optional device tensor of ``nq * nframes`` 64-bit entries, which receives the
         sums instead -- the call is then asynchronous and returns ``out``."""
-        stride = w if stride is None else stride
-        frame_pitch = stride * h if frame_pitch is None else frame_pitch
-        nn = (self.n or 0) ** 2
-        qs = np.ascontiguousarray(np.asarray(qs, dtype=np.uint16).reshape(-1, nn) if nn else
-                                  np.asarray(qs, dtype=np.uint16))
-        nq = qs.shape[0] if nn else 1
-        u64p = C.POINTER(C.c_uint64)
-        if out is not None:
-            if _nbytes(out) < 8 * nq * nframes:
-                raise IEError(IE_EINVAL, "probe_gop: out holds fewer than nq * nframes 64-bit entries")
-            self._chk(self.L.ie_probe_gop(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, gop, merange, int(rle),
-                                          qs.ctypes.data, nq, C.cast(C.c_void_p(_ptr(out)), u64p)))
-            return out
-        bits = np.zeros((max(nq, 1), nframes), dtype=np.uint64)
-        self._chk(self.L.ie_probe_gop(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, gop, merange, int(rle),
-                                      qs.ctypes.data, nq, bits.ctypes.data_as(u64p)))
-        return bits
+        return self._probe("probe_gop", False, y, w, h, qs, nframes, (gop, merange, int(rle)), stride, frame_pitch, out)
 
     def probe_rd(self, y, w: int, h: int, qs, nframes: int = 1, rle: bool = True, stride: int | None = None,
                  frame_pitch: int | None = None, out=None):
@@ -674,26 +668,7 @@ class Codec:
         codec's own matrix is left as it was.  ``out``: an optional pair ``(bits, sse)`` of device
         tensors of ``nq * nframes`` 64-bit entries each (``bits`` may be None), which receive the
         sums instead -- the call is then asynchronous and returns ``out``."""
-        stride = w if stride is None else stride
-        frame_pitch = stride * h if frame_pitch is None else frame_pitch
-        nn = (self.n or 0) ** 2
-        qs = np.ascontiguousarray(np.asarray(qs, dtype=np.uint16).reshape(-1, nn) if nn else
-                                  np.asarray(qs, dtype=np.uint16))
-        nq = qs.shape[0] if nn else 1
-        u64p = C.POINTER(C.c_uint64)
-        if out is not None:
-            dbits, dsse = out
-            if any(t is not None and _nbytes(t) < 8 * nq * nframes for t in (dbits, dsse)):
-                raise IEError(IE_EINVAL, "probe_rd: out holds fewer than nq * nframes 64-bit entries")
-            self._chk(self.L.ie_probe_rd(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, int(rle), qs.ctypes.data,
-                                         nq, None if dbits is None else C.cast(C.c_void_p(_ptr(dbits)), u64p),
-                                         None if dsse is None else C.cast(C.c_void_p(_ptr(dsse)), u64p)))
-            return out
-        bits = np.zeros((max(nq, 1), nframes), dtype=np.uint64)
-        sse = np.zeros((max(nq, 1), nframes), dtype=np.uint64)
-        self._chk(self.L.ie_probe_rd(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, int(rle), qs.ctypes.data,
-                                     nq, bits.ctypes.data_as(u64p), sse.ctypes.data_as(u64p)))
-        return bits, sse
+        return self._probe("probe_rd", True, y, w, h, qs, nframes, (int(rle),), stride, frame_pitch, out)
 
     def probe_gop_rd(self, y, w: int, h: int, qs, gop: int, merange: int, nframes: int = 1, rle: bool = True,
                      motioncomp: bool = True, stride: int | None = None, frame_pitch: int | None = None, out=None):
@@ -706,28 +681,8 @@ class Codec:
         optional pair ``(bits, sse)`` of device tensors of ``nq * nframes`` 64-bit entries each
         (``bits`` may be None), which receive the sums instead -- the call is then asynchronous and
         returns ``out``."""
-        stride = w if stride is None else stride
-        frame_pitch = stride * h if frame_pitch is None else frame_pitch
-        nn = (self.n or 0) ** 2
-        qs = np.ascontiguousarray(np.asarray(qs, dtype=np.uint16).reshape(-1, nn) if nn else
-                                  np.asarray(qs, dtype=np.uint16))
-        nq = qs.shape[0] if nn else 1
-        u64p = C.POINTER(C.c_uint64)
-        if out is not None:
-            dbits, dsse = out
-            if any(t is not None and _nbytes(t) < 8 * nq * nframes for t in (dbits, dsse)):
-                raise IEError(IE_EINVAL, "probe_gop_rd: out holds fewer than nq * nframes 64-bit entries")
-            self._chk(self.L.ie_probe_gop_rd(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, gop, merange, int(rle),
-                                             int(motioncomp), qs.ctypes.data, nq,
-                                             None if dbits is None else C.cast(C.c_void_p(_ptr(dbits)), u64p),
-                                             None if dsse is None else C.cast(C.c_void_p(_ptr(dsse)), u64p)))
-            return out
-        bits = np.zeros((max(nq, 1), nframes), dtype=np.uint64)
-        sse = np.zeros((max(nq, 1), nframes), dtype=np.uint64)
-        self._chk(self.L.ie_probe_gop_rd(self.h, _ptr(y), w, h, stride, frame_pitch, nframes, gop, merange, int(rle),
-                                         int(motioncomp), qs.ctypes.data, nq, bits.ctypes.data_as(u64p),
-                                         sse.ctypes.data_as(u64p)))
-        return bits, sse
+        return self._probe("probe_gop_rd", True, y, w, h, qs, nframes, (gop, merange, int(rle), int(motioncomp)), stride,
+                           frame_pitch, out)
 
     def host_array(self, nbytes: int) -> np.ndarray:
         """A uint8 numpy array in page-locked host memory (ie_host_alloc): host buffers the
@@ -807,8 +762,7 @@ class Codec:
     def decode_frames(self, stream, w: int, h: int, out, start_bit: int = 0, nframes: int = 1, rle: bool = True,
                       stride: int | None = None, frame_pitch: int | None = None, length: int | None = None) -> int:
         """Decode ``nframes`` frames of block records from bit ``start_bit``; returns the end bit."""
-        stride = w if stride is None else stride
-        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        stride, frame_pitch = _pitches(w, h, stride, frame_pitch)
         end = C.c_uint64(0)
         n = _nbytes(stream) if length is None else length
         self._chk(self.L.ie_decode_frames(self.h, _ptr(stream), n, start_bit, w, h, nframes, int(rle), _ptr(out),
@@ -823,8 +777,7 @@ class Codec:
         numpy arrays (host) or torch tensors (device).  Returns the end bits (uint64, one per
         image); raises :class:`IEError` (``IE_EFORMAT``, the message names the image) when an
         image's stream ends before its last block -- the other images are decoded all the same."""
-        stride = w if stride is None else stride
-        frame_pitch = stride * h if frame_pitch is None else frame_pitch
+        stride, frame_pitch = _pitches(w, h, stride, frame_pitch)
         nb = np.ascontiguousarray(nbits, dtype=np.uint64)
         eb = np.zeros(max(nb.size, 1), dtype=np.uint64)
         u64p = C.POINTER(C.c_uint64)
@@ -842,8 +795,7 @@ class Codec:
         array.  Returns ``(out, end_bit)``: the whole stream is parsed, the end bit is the full
         decode's."""
         x0, y0, rw, rh = (int(v) for v in rect)
-        stride = rw if stride is None else stride
-        frame_pitch = stride * rh if frame_pitch is None else frame_pitch
+        stride, frame_pitch = _pitches(rw, rh, stride, frame_pitch)
         if out is None:
             if stride != rw or frame_pitch != rw * rh:
                 raise IEError(IE_EINVAL, "decode_region: a stride or frame_pitch needs an out buffer")
@@ -861,8 +813,7 @@ class Codec:
         array.  Returns ``(out, end_bits)``; raises :class:`IEError` (``IE_EFORMAT``, the message
         names the image) when an image's stream ends before its last block, wherever that is."""
         x0, y0, rw, rh = (int(v) for v in rect)
-        stride = rw if stride is None else stride
-        frame_pitch = stride * rh if frame_pitch is None else frame_pitch
+        stride, frame_pitch = _pitches(rw, rh, stride, frame_pitch)
         nb = np.ascontiguousarray(nbits, dtype=np.uint64)
         if out is None:
             if stride != rw or frame_pitch != rw * rh:
@@ -880,8 +831,7 @@ class Codec:
         ``w // scale`` bytes (a scale the library will refuse sizes ``out`` as scale 1)."""
         s = scale if isinstance(scale, int) and scale > 0 else 1
         ow, oh = max(w // s, 0), max(h // s, 0)
-        stride = ow if stride is None else stride
-        frame_pitch = stride * oh if frame_pitch is None else frame_pitch
+        stride, frame_pitch = _pitches(ow, oh, stride, frame_pitch)
         if out is None:
             if stride != ow or frame_pitch != ow * oh:
                 raise IEError(IE_EINVAL, what + ": a stride or frame_pitch needs an out buffer")

@@ -63,6 +63,30 @@ std::string fmt(const char* f, double a, double b = 0, double c = 0) {
     return buf;
 }
 
+FileParams image_params(int w, int h, int n, const uint16_t* q, bool rle, bool huffman, int mode) {
+    FileParams p;
+    p.w = w;
+    p.h = h;
+    p.n = n;
+    p.q = q;
+    p.rle = rle;
+    p.huffman = huffman;
+    p.mode = mode;
+    return p;
+}
+
+// A video of `len` bytes of Y + UV frames (VideoBase.cpp:8-9); false unless it holds 1..32767 of them
+bool video_params(int w, int h, int n, const uint16_t* q, bool rle, bool huffman, int mode, size_t len, int gop,
+                  int merange, FileParams* p) {
+    *p = image_params(w, h, n, q, rle, huffman, mode);
+    p->video = true;
+    p->frame_pitch = size_t(w) * h + size_t(w) * h / 2;
+    p->frames = int(std::min<size_t>(p->frame_pitch ? len / p->frame_pitch : 0, 32768));  // (no wrap-around into range)
+    p->gop = gop < 1 ? 1 : gop;
+    p->merange = merange;
+    return p->frames > 0 && p->frames <= 32767;
+}
+
 }  // namespace
 
 ie_ctx* Device::get() {
@@ -489,14 +513,7 @@ bool ImageEncoder::process() {
     const int n = quant_m.n;
     if (width % n || height % n) return (err_ = "width and height must be multiples of the block size", false);
     if (raw.size() != size_t(width) * height) return (err_ = "raw file size differs from width x height", false);
-    FileParams p;
-    p.w = width;
-    p.h = height;
-    p.n = n;
-    p.q = quant_m.q.data();
-    p.rle = use_rle;
-    p.huffman = opt_.huffman;
-    p.mode = opt_.mode;
+    const FileParams p = image_params(width, height, n, quant_m.q.data(), use_rle, opt_.huffman, opt_.mode);
     return encode_file(Device::get(), raw.data(), p, result_, err_) == IE_OK;
 }
 
@@ -551,22 +568,9 @@ bool VideoEncoder::process() {
     util::Logger::WriteLn("[VideoEncoder] Processing video...");
     const int n = quant_m.n;
     if (width % n || height % n) return (err_ = "width and height must be multiples of the block size", false);
-    const size_t pitch = size_t(width) * height + size_t(width) * height / 2;  // Y + UV (VideoBase.cpp:8-9)
-    const size_t frames = pitch ? raw_size / pitch : 0;
-    if (frames == 0 || frames > 32767) return (err_ = "frame count must be in 1..32767", false);
     FileParams p;
-    p.w = width;
-    p.h = height;
-    p.n = n;
-    p.q = quant_m.q.data();
-    p.rle = use_rle;
-    p.huffman = opt_.huffman;
-    p.mode = opt_.mode;
-    p.video = true;
-    p.frames = int(frames);
-    p.gop = gop;
-    p.merange = merange;
-    p.frame_pitch = pitch;
+    if (!video_params(width, height, n, quant_m.q.data(), use_rle, opt_.huffman, opt_.mode, raw_size, gop, merange, &p))
+        return (err_ = "frame count must be in 1..32767", false);
     return encode_video_streamed(Device::get(), source_file, p, result_, err_) == IE_OK;
 }
 
@@ -644,13 +648,7 @@ extern "C" {
 int64_t ieh_write_header(uint8_t* out, size_t cap, int n, const uint16_t* q, int rle, int w, int h, int huffman,
                          int video, int frames, int gop, int merange) {
     if (!out || !q || (n != 4 && n != 8)) return IE_EINVAL;
-    dc::FileParams p;
-    p.w = w;
-    p.h = h;
-    p.n = n;
-    p.q = q;
-    p.rle = rle != 0;
-    p.huffman = huffman != 0;
+    dc::FileParams p = dc::image_params(w, h, n, q, rle != 0, huffman != 0, IE_MODE_FAST);
     p.video = video != 0;
     p.frames = frames;
     p.gop = gop;
@@ -667,14 +665,7 @@ int64_t ieh_write_header(uint8_t* out, size_t cap, int n, const uint16_t* q, int
 int64_t ieh_encode_image(ie_ctx* c, const uint8_t* y, int w, int h, const uint16_t* q, int n, int rle, int huffman,
                          int mode, uint8_t* out, size_t cap) {
     if (!c || !y || !q || !out) return IE_EINVAL;
-    dc::FileParams p;
-    p.w = w;
-    p.h = h;
-    p.n = n;
-    p.q = q;
-    p.rle = rle != 0;
-    p.huffman = huffman != 0;
-    p.mode = mode;
+    const dc::FileParams p = dc::image_params(w, h, n, q, rle != 0, huffman != 0, mode);
     std::vector<uint8_t> v;
     std::string err;
     const int r = dc::encode_file(c, y, p, v, err);
@@ -901,13 +892,7 @@ int64_t ieh_encode_image_budget(ie_ctx* c, const uint8_t* y, int w, int h, const
     if (!c || !y || !base || !out || !percent || (n != 4 && n != 8)) return IE_EINVAL;
     int r;
     if ((r = ie_set_quant(c, base, n))) return r;  // the probe's block size and transform tables
-    dc::FileParams p;
-    p.w = w;
-    p.h = h;
-    p.n = n;
-    p.rle = rle != 0;
-    p.huffman = huffman != 0;
-    p.mode = mode;
+    const dc::FileParams p = dc::image_params(w, h, n, nullptr, rle != 0, huffman != 0, mode);
     const uint8_t* dy;
     if ((r = frame_on_device(c, y, w, h, &dy))) return r;
     return encode_budget(c, dy, p, base, budget_bytes, out, cap, percent);
@@ -919,13 +904,7 @@ int64_t ieh_encode_image_quality(ie_ctx* c, const uint8_t* y, int w, int h, cons
     if (!c || !y || !base || !out || !percent || !sse || (n != 4 && n != 8)) return IE_EINVAL;
     int r;
     if ((r = ie_set_quant(c, base, n))) return r;  // the probe's block size and transform tables
-    dc::FileParams p;
-    p.w = w;
-    p.h = h;
-    p.n = n;
-    p.rle = rle != 0;
-    p.huffman = huffman != 0;
-    p.mode = mode;
+    const dc::FileParams p = dc::image_params(w, h, n, nullptr, rle != 0, huffman != 0, mode);
     const uint8_t* dy;
     if ((r = frame_on_device(c, y, w, h, &dy))) return r;
     return encode_quality(c, dy, p, base, max_sse, 1, out, cap, percent, sse, nullptr);
@@ -940,19 +919,7 @@ int64_t ieh_encode_video_gop(ie_ctx* c, const uint8_t* yuv, size_t len, int w, i
                              int rle, int huffman, int gop, int merange, int mode, uint8_t* out, size_t cap) {
     if (!c || !yuv || !q || !out || w <= 0 || h <= 0) return IE_EINVAL;
     dc::FileParams p;
-    p.w = w;
-    p.h = h;
-    p.n = n;
-    p.q = q;
-    p.rle = rle != 0;
-    p.huffman = huffman != 0;
-    p.mode = mode;
-    p.video = true;
-    p.frame_pitch = size_t(w) * h + size_t(w) * h / 2;
-    p.frames = int(len / p.frame_pitch);
-    p.gop = gop < 1 ? 1 : gop;
-    p.merange = merange;
-    if (p.frames <= 0 || p.frames > 32767) return IE_EINVAL;
+    if (!dc::video_params(w, h, n, q, rle != 0, huffman != 0, mode, len, gop, merange, &p)) return IE_EINVAL;
     std::vector<uint8_t> v;
     std::string err;
     const int r = dc::encode_file(c, yuv, p, v, err);
@@ -967,18 +934,7 @@ int64_t ieh_encode_video_budget(ie_ctx* c, const uint8_t* yuv, size_t len, int w
                                 size_t cap, int* percent) {
     if (!c || !yuv || !base || !out || !percent || (n != 4 && n != 8) || w <= 0 || h <= 0) return IE_EINVAL;
     dc::FileParams p;
-    p.w = w;
-    p.h = h;
-    p.n = n;
-    p.rle = rle != 0;
-    p.huffman = huffman != 0;
-    p.mode = mode;
-    p.video = true;
-    p.frame_pitch = size_t(w) * h + size_t(w) * h / 2;
-    p.frames = int(len / p.frame_pitch);
-    p.gop = gop < 1 ? 1 : gop;
-    p.merange = merange;
-    if (p.frames <= 0 || p.frames > 32767) return IE_EINVAL;
+    if (!dc::video_params(w, h, n, nullptr, rle != 0, huffman != 0, mode, len, gop, merange, &p)) return IE_EINVAL;
     int r;
     if ((r = ie_set_quant(c, base, n))) return r;  // the probe's block size and transform tables
     const uint8_t* dy;
@@ -991,18 +947,7 @@ int64_t ieh_encode_video_quality(ie_ctx* c, const uint8_t* yuv, size_t len, int 
                                  uint8_t* out, size_t cap, int* percent, uint64_t* sse, uint64_t* frame_sse) {
     if (!c || !yuv || !base || !out || !percent || !sse || (n != 4 && n != 8) || w <= 0 || h <= 0) return IE_EINVAL;
     dc::FileParams p;
-    p.w = w;
-    p.h = h;
-    p.n = n;
-    p.rle = rle != 0;
-    p.huffman = huffman != 0;
-    p.mode = mode;
-    p.video = true;
-    p.frame_pitch = size_t(w) * h + size_t(w) * h / 2;
-    p.frames = int(len / p.frame_pitch);
-    p.gop = gop < 1 ? 1 : gop;
-    p.merange = merange;
-    if (p.frames <= 0 || p.frames > 32767) return IE_EINVAL;
+    if (!dc::video_params(w, h, n, nullptr, rle != 0, huffman != 0, mode, len, gop, merange, &p)) return IE_EINVAL;
     int r;
     if ((r = ie_set_quant(c, base, n))) return r;  // the probe's block size and transform tables
     const uint8_t* dy;

@@ -1,23 +1,33 @@
-// imageencoder_amd/csrc/ie_capi_probe.cpp -- ie_probe_sizes: the payload bits of a batch of frames
-// under many candidate quantisation matrices, from one pass over the pixels (ie_probe.hip), and
-// ie_probe_rd: the squared error of the decoded pixels as well.  They read the context's P / S / R
-// tables (they depend on the block size only) and leave its matrix, tables, chain state and end
-// bits alone.
+// imageencoder_amd/csrc/ie_capi_probe.cpp -- the rate-control probes: what a batch of frames would
+// cost under many candidate quantisation matrices, without writing a stream.
+//   ie_probe_sizes   the payload bits of independent frames, one pass over the pixels (ie_probe.hip)
+//   ie_probe_rd      and the squared error of the decoded pixels
+//   ie_probe_gop     the payload bits of every frame of a video with P-frames
+//   ie_probe_gop_rd  and the squared error of the pixels ie_decode_gop would write
+// They read the context's P / S / R tables (which depend on the block size only) and leave its
+// matrix, tables, chain state, end bits and the encoders' gop scratch alone.
+//
+// The gop probes.  I-frames go through the kernels of the first two calls; P-frames with 4x4 blocks
+// through pf_probe_kernel (ie_pframe.hip), one set of launches per step j = 1 .. gop-1 over the
+// groups of a wave that have such a frame, every (group, candidate) pair with frames of scratch of
+// its own in d_probe_gop.  ie_probe_gop: two reconstructed frames per pair, alternating; the
+// I-frames of the whole video in one launch, scattered into the table.  P-frames with 8x8 blocks
+// carry vectors only (ImageBase.cpp:271): their size is a constant and no macroblock kernel runs.
+// ie_probe_gop_rd: the decoder's frames are a chain of their own next to the encoder's
+// reconstructions -- a group's decoder starts from the LOSSY decoded I-frame (the encoder's first
+// P-frame predicts from the I-frame's source), copies its blocks at the vector as the stream holds
+// it and adds the error as the record holds it -- so a pair owns four frames, two reconstructions
+// and two decoded frames; per wave probe_kernel<4, true, true> over the wave's I-frames (bits,
+// squared error, the decoded pixels stored into the pairs' first decoded frame), then
+// pf_probe_kernel<PgRdArgs> per step.
 #include "ie_ctx.hpp"
+#include "ie_encode_blocks.h"
 
 using namespace iec;
 
 namespace {
-// algo.cpp:68-87: natural index of zig-zag position z (the kernel's lanes are zig-zag positions)
-const uint8_t kZz4[16] = {0, 1, 4, 8, 5, 2, 3, 6, 9, 12, 13, 10, 7, 11, 14, 15};
-const uint8_t kZz8[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                          41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                          30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-}  // namespace
-
-namespace iec {
-
+// nq in [1, IE_PROBE_MAX] and no zero entry, else IE_EINVAL (the message names the matrix)
 int check_candidates(ie_ctx* c, const uint16_t* q, int nq) {
     if (nq < 1 || nq > IE_PROBE_MAX)
         return fail(c, IE_EINVAL, "nq must be in [1, " + std::to_string(int(IE_PROBE_MAX)) + "]");
@@ -29,17 +39,21 @@ int check_candidates(ie_ctx* c, const uint16_t* q, int nq) {
     return IE_OK;
 }
 
-// (an earlier call's copy out of the pinned block may still be in flight when the calls are
-// asynchronous: the event after it is waited for before the block is written again)
-int stage_candidates(ie_ctx* c, const uint16_t* q, int nq) {
+// Host frames to d_in (*dy; device frames are read in place), then the candidates in zig-zag order
+// to d_probe_q on the stream, through pinned memory.  (An earlier call's copy out of the pinned block
+// may still be in flight when the calls are asynchronous: the event after it is waited for before
+// the block is written again.)
+int stage(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes, const uint16_t* q,
+          int nq, const uint8_t** dy) {
+    int r;
+    if ((r = stage_in(c, y, is_device_ptr(y), frames_span(nframes, frame_pitch, stride, w, h), dy))) return r;
     const int n = c->n, nn = n * n;
     const size_t qcap = size_t(IE_PROBE_MAX) * 64;
-    int r;
     if ((r = c->h_probe_q.reserve(c, qcap))) return r;
     if ((r = c->d_probe_q.reserve(c, qcap))) return r;
     if ((r = c->ev_probe.create(c, hipEventDisableTiming))) return r;
     if (c->probe_recorded) HIPCHK(c, hipEventSynchronize(c->ev_probe));
-    const uint8_t* zz = n == 4 ? kZz4 : kZz8;
+    const int* zz = n == 4 ? ie::ZigZag<4>::idx : ie::ZigZag<8>::idx;  // natural index of zig-zag position z
     for (int m = 0; m < nq; m++)
         for (int z = 0; z < nn; z++) c->h_probe_q[size_t(m) * nn + z] = q[size_t(m) * nn + zz[z]];
     HIPCHK(c, hipMemcpyAsync(c->d_probe_q, c->h_probe_q, size_t(nq) * nn * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
@@ -48,73 +62,195 @@ int stage_candidates(ie_ctx* c, const uint16_t* q, int nq) {
     return IE_OK;
 }
 
-}  // namespace iec
+// Where a call's sums go.  sse == nullptr: a size probe (bits required); else bits is optional.
+// Device results: the caller's arrays, the call asynchronous on the context's stream.  Host
+// results: one block of d_probe_bits (the bits, then the squared errors), read back by finish().
+struct Results {
+    uint64_t *bits, *sse;  // the caller's
+    size_t nsums;          // nq * nframes, the entries of each
+    bool dev = false;
+    uint64_t *dbits = nullptr, *dsse = nullptr;  // where the kernels add (dbits: nullptr when bits is)
+    uint64_t* extra = nullptr;                   // place()'s further sums, in d_probe_bits
 
-namespace {
-// Both entry points.  sse == nullptr: ie_probe_sizes (bits required); else ie_probe_rd (bits optional).
+    int check(ie_ctx* c) {
+        dev = is_device_ptr(sse ? sse : bits);
+        if (sse && bits && is_device_ptr(bits) != dev)
+            return fail(c, IE_EINVAL, "bits and sse must be both host or both device memory");
+        if (dev && bits && reinterpret_cast<uintptr_t>(bits) % 8) return fail(c, IE_EINVAL, "device bits must be 8-byte aligned");
+        if (dev && sse && reinterpret_cast<uintptr_t>(sse) % 8) return fail(c, IE_EINVAL, "device sse must be 8-byte aligned");
+        return IE_OK;
+    }
+    // Reserves what the call needs of d_probe_bits and h_probe_out and zeroes every sum;
+    // nextra: further sums of the call's own (ie_probe_gop's I-frames), after the results.
+    int place(ie_ctx* c, size_t nextra = 0) {
+        const size_t own = dev ? 0 : nsums * (sse ? 2 : 1);
+        int r;
+        if (own + nextra && (r = c->d_probe_bits.reserve(c, own + nextra))) return r;
+        if (!dev && sse && (r = c->h_probe_out.reserve(c, own))) return r;
+        extra = c->d_probe_bits + own;
+        if (!dev) {
+            dbits = c->d_probe_bits;
+            dsse = sse ? dbits + nsums : nullptr;
+            HIPCHK(c, hipMemsetAsync(dbits, 0, own * sizeof(uint64_t), c->stream));
+        } else {
+            dbits = bits;
+            dsse = sse;
+            if (dbits) HIPCHK(c, hipMemsetAsync(dbits, 0, nsums * sizeof(uint64_t), c->stream));
+            if (dsse) HIPCHK(c, hipMemsetAsync(dsse, 0, nsums * sizeof(uint64_t), c->stream));
+        }
+        if (nextra) HIPCHK(c, hipMemsetAsync(extra, 0, nextra * sizeof(uint64_t), c->stream));
+        return IE_OK;
+    }
+    int finish(ie_ctx* c) const {
+        if (dev) return IE_OK;  // asynchronous on the context's stream
+        if (!sse) {
+            HIPCHK(c, hipMemcpyAsync(bits, dbits, nsums * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            return IE_OK;
+        }
+        // one read-back for both arrays, through pinned memory
+        HIPCHK(c, hipMemcpyAsync(c->h_probe_out, dbits, nsums * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (bits) std::copy(c->h_probe_out + 0, c->h_probe_out + nsums, bits);
+        std::copy(c->h_probe_out + nsums, c->h_probe_out + 2 * nsums, sse);
+        return IE_OK;
+    }
+};
+
+// probe_kernel's arguments for the frames the launch reads: nframes frames from y, `pitch` apart,
+// under candidates [m0, m0 + nm).  Rows are read with 4-byte loads when every row starts on one.
+ie::ProbeArgs probe_args(const ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t pitch, int nframes,
+                         int use_rle, int m0, int nm, uint64_t* bits) {
+    const int n = c->n;
+    ie::ProbeArgs a{};
+    a.y = y;
+    a.stride = stride;
+    a.frame_pitch = pitch;
+    a.bx = w / n;
+    a.by = h / n;
+    a.nframes = nframes;
+    a.rle = use_rle ? 1 : 0;
+    a.vec_ok = (reinterpret_cast<uintptr_t>(y) % 4 == 0 && stride % 4 == 0 && (nframes == 1 || pitch % 4 == 0)) ? 1 : 0;
+    a.nq = nm;
+    a.q = c->d_probe_q + size_t(m0) * n * n;
+    a.tab = c->d_tab;
+    a.bits = reinterpret_cast<unsigned long long*>(bits);
+    return a;
+}
+
+// Both entry points without P-frames.  sse == nullptr: ie_probe_sizes; else ie_probe_rd.
 int probe(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes, int use_rle,
           const uint16_t* q, int nq, uint64_t* bits, uint64_t* sse, bool rd) {
     if (!c || !y || !q || (rd ? !sse : !bits)) return IE_EINVAL;
     int r = check_frames(c, w, h, nframes, stride, frame_pitch);
     if (r) return r;
     if ((r = check_candidates(c, q, nq))) return r;
-    const int n = c->n;
     HIPCHK(c, hipSetDevice(c->device));
-    const bool in_dev = is_device_ptr(y);
-    const bool res_dev = is_device_ptr(rd ? sse : bits);
-    if (rd && bits && is_device_ptr(bits) != res_dev)
-        return fail(c, IE_EINVAL, "bits and sse must be both host or both device memory");
-    if (res_dev && bits && reinterpret_cast<uintptr_t>(bits) % 8) return fail(c, IE_EINVAL, "device bits must be 8-byte aligned");
-    if (res_dev && rd && reinterpret_cast<uintptr_t>(sse) % 8) return fail(c, IE_EINVAL, "device sse must be 8-byte aligned");
-
+    Results res{bits, sse, size_t(nq) * size_t(nframes)};
     const uint8_t* dy;
-    if ((r = stage_in(c, y, in_dev, frames_span(nframes, frame_pitch, stride, w, h), &dy))) return r;
-
-    if ((r = stage_candidates(c, q, nq))) return r;
-
-    // host results: the sums (ie_probe_rd: the bits, then the squared errors) in one device block
-    const size_t nsums = size_t(nq) * size_t(nframes);
-    uint64_t *dbits = bits, *dsse = sse;
-    if (!res_dev) {
-        if ((r = c->d_probe_bits.reserve(c, nsums * (rd ? 2 : 1)))) return r;
-        dbits = c->d_probe_bits;
-        dsse = rd ? dbits + nsums : nullptr;
-        if (rd && (r = c->h_probe_out.reserve(c, nsums * 2))) return r;
-        HIPCHK(c, hipMemsetAsync(dbits, 0, nsums * (rd ? 2 : 1) * sizeof(uint64_t), c->stream));
-    } else {
-        if (dbits) HIPCHK(c, hipMemsetAsync(dbits, 0, nsums * sizeof(uint64_t), c->stream));
-        if (rd) HIPCHK(c, hipMemsetAsync(dsse, 0, nsums * sizeof(uint64_t), c->stream));
-    }
-
-    ie::ProbeArgs a{};
-    a.y = dy;
-    a.stride = stride;
-    a.frame_pitch = frame_pitch;
-    a.bx = w / n;
-    a.by = h / n;
-    a.nframes = nframes;
-    a.rle = use_rle ? 1 : 0;
-    a.vec_ok = (reinterpret_cast<uintptr_t>(dy) % 4 == 0 && stride % 4 == 0 && (nframes == 1 || frame_pitch % 4 == 0)) ? 1 : 0;
-    a.nq = nq;
-    a.q = c->d_probe_q;
-    a.tab = c->d_tab;
-    a.bits = reinterpret_cast<unsigned long long*>(dbits);
+    if ((r = res.check(c)) || (r = stage(c, y, w, h, stride, frame_pitch, nframes, q, nq, &dy)) || (r = res.place(c))) return r;
+    const ie::ProbeArgs a = probe_args(c, dy, w, h, stride, frame_pitch, nframes, use_rle, 0, nq, res.dbits);
     if (rd)
-        ie::launch_probe_rd(a, reinterpret_cast<unsigned long long*>(dsse), n, c->stream);
+        ie::launch_probe_rd(a, reinterpret_cast<unsigned long long*>(res.dsse), c->n, c->stream);
     else
-        ie::launch_probe_sizes(a, n, c->stream);
+        ie::launch_probe_sizes(a, c->n, c->stream);
     HIPCHK(c, hipGetLastError());
-    if (res_dev) return IE_OK;  // asynchronous on the context's stream
-    if (!rd) {
-        HIPCHK(c, hipMemcpyAsync(bits, dbits, nsums * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return IE_OK;
+    return res.finish(c);
+}
+
+// ---- the P-frame steps of the gop probes (4x4 blocks)
+struct GopCall {  // what the two calls share, after their checks and staging
+    const uint8_t* dy;
+    int w, h;
+    size_t stride, frame_pitch;
+    int nframes, gop, merange, use_rle, nq;
+    uint64_t* dbits;  // the table of bits (ie_probe_gop_rd: may be nullptr)
+};
+
+struct GopPlan {
+    size_t fpx, pair_bytes;  // bytes of a frame, of a pair's scratch
+    int Gp;                  // groups with a P-frame
+    int chunk, Gw;           // candidates, groups of a wave
+};
+// Waves: at most `pairs` (group, candidate) pairs hold scratch at a time, pair_frames frames each --
+// what keeps it under 1 GiB, lowered further by IE_PROBE_GOP_MAX (read on every call).  Whole groups
+// with all candidates while that many fit; otherwise one group at a time, chunks of candidates.
+// Grows d_probe_gop to hold a wave.
+int gop_plan(ie_ctx* c, const GopCall& g, int pair_frames, GopPlan* pl) {
+    pl->fpx = size_t(g.w) * g.h;
+    pl->pair_bytes = size_t(pair_frames) * pl->fpx;
+    size_t pairs = std::max<size_t>(1, (size_t(1) << 30) / pl->pair_bytes);
+    if (const char* eb = getenv("IE_PROBE_GOP_MAX"))
+        if (atoll(eb) > 0) pairs = std::min<size_t>(pairs, size_t(atoll(eb)));
+    pl->Gp = (g.nframes - 1 + g.gop - 1) / g.gop;
+    pl->chunk = int(std::min<size_t>(pairs, size_t(g.nq)));
+    pl->Gw = pl->chunk < g.nq ? 1 : int(std::min<size_t>({size_t(pl->Gp), pairs / size_t(g.nq), size_t(65535)}));
+    return c->d_probe_gop.reserve(c, size_t(pl->Gw) * size_t(pl->chunk) * pl->pair_bytes);
+}
+
+// The fields of step j that both probes set (Args: PgArgs or PgRdArgs), for the wave that starts
+// at frame f0 and candidates [m0, m0 + nm); `last`: no later step reads this one's frames.
+// Returns the table index of candidate m0, frame f0 + j.
+size_t pg_step(ie::PgArgs& a, const ie_ctx* c, const GopCall& g, const GopPlan& pl, int f0, int m0, int nm, int j, bool last) {
+    const size_t group_pitch = size_t(g.gop) * g.frame_pitch;
+    a.cur = g.dy + size_t(f0 + j) * g.frame_pitch;
+    a.cs = g.stride;
+    a.g_cur = group_pitch;
+    a.g_rec = size_t(pl.chunk) * pl.pair_bytes;
+    a.m_rec = pl.pair_bytes;
+    if (j == 1) {  // the I-frame as the caller holds it, shared by the candidates
+        a.ref = g.dy + size_t(f0) * g.frame_pitch;
+        a.rs = g.stride;
+        a.g_ref = group_pitch;
+        a.m_ref = 0;
+    } else {       // every candidate's own reconstruction of the previous P-frame
+        a.ref = c->d_probe_gop + size_t((j - 1) & 1) * pl.fpx;
+        a.rs = size_t(g.w);
+        a.g_ref = a.g_rec;
+        a.m_ref = a.m_rec;
     }
-    // one read-back for both arrays, through pinned memory
-    HIPCHK(c, hipMemcpyAsync(c->h_probe_out, dbits, nsums * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (bits) std::copy(c->h_probe_out + 0, c->h_probe_out + nsums, bits);
-    std::copy(c->h_probe_out + nsums, c->h_probe_out + 2 * nsums, sse);
+    a.rec = last ? nullptr : c->d_probe_gop + size_t(j & 1) * pl.fpx;
+    a.w = g.w;
+    a.h = g.h;
+    a.mbx = g.w / 16;
+    a.mby = g.h / 16;
+    a.rle = g.use_rle ? 1 : 0;
+    a.merange = g.merange;
+    a.mv_bits = mvec_bits(g.merange);
+    a.tab = c->d_tab;
+    a.q = c->d_probe_q + size_t(m0) * 16;
+    a.nm = nm;
+    a.mper = j == 1 ? nm : 1;  // a shared reference: the candidates loop inside the wave
+    const size_t at = size_t(m0) * size_t(g.nframes) + size_t(f0 + j);
+    a.bits = g.dbits ? reinterpret_cast<unsigned long long*>(g.dbits) + at : nullptr;
+    a.m_bits = uint64_t(g.nframes);
+    a.g_bits = uint64_t(g.gop);
+    return at;
+}
+
+// The waves, their chunks of candidates and their steps.  wave(f0, gw, m0, nm) -> IE_* runs before
+// the steps of a chunk (gw groups from frame f0); step(a, j, last, at, gj) launches step j over
+// the gj groups that have a frame j, from the arguments pg_step filled.
+template <class Args, class Wave, class Step>
+int gop_waves(ie_ctx* c, const GopCall& g, const GopPlan& pl, Wave wave, Step step) {
+    int r;
+    for (int g0 = 0; g0 < pl.Gp; g0 += pl.Gw) {
+        const int gw = std::min(pl.Gw, pl.Gp - g0);
+        const int f0 = g0 * g.gop;
+        const int nfw = int(std::min<int64_t>(int64_t(g.nframes) - f0, int64_t(gw) * g.gop));
+        const int steps = std::min(g.gop, nfw);  // frames of the wave's longest group
+        for (int m0 = 0; m0 < g.nq; m0 += pl.chunk) {
+            const int nm = std::min(pl.chunk, g.nq - m0);
+            if ((r = wave(f0, gw, m0, nm))) return r;
+            for (int j = 1; j < steps; j++) {
+                const bool last = j + 1 >= steps;
+                Args a{};
+                const size_t at = pg_step(a, c, g, pl, f0, m0, nm, j, last);
+                step(a, j, last, at, std::min(gw, (nfw - j + g.gop - 1) / g.gop));
+                HIPCHK(c, hipGetLastError());
+            }
+        }
+    }
     return IE_OK;
 }
 }  // namespace
@@ -127,4 +263,109 @@ extern "C" int ie_probe_sizes(ie_ctx* c, const uint8_t* y, int w, int h, size_t 
 extern "C" int ie_probe_rd(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,
                            int use_rle, const uint16_t* q, int nq, uint64_t* bits, uint64_t* sse) {
     return probe(c, y, w, h, stride, frame_pitch, nframes, use_rle, q, nq, bits, sse, true);
+}
+
+extern "C" int ie_probe_gop(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,
+                            int gop, int merange, int use_rle, const uint16_t* q, int nq, uint64_t* bits) {
+    if (!c || !y || !q || !bits) return IE_EINVAL;
+    gop = std::max(1, gop);
+    size_t need = 0;
+    int r = check_gop(c, w, h, stride, frame_pitch, nframes, gop, merange, SIZE_MAX, 0, &need);
+    if (r) return r;
+    if ((r = check_candidates(c, q, nq))) return r;
+    if (gop <= 1 || nframes == 1)  // no P-frame
+        return ie_probe_sizes(c, y, w, h, stride, frame_pitch, nframes, use_rle, q, nq, bits);
+    HIPCHK(c, hipSetDevice(c->device));
+    Results res{bits, nullptr, size_t(nq) * size_t(nframes)};
+    const uint8_t* dy;
+    const int n = c->n, G = (nframes + gop - 1) / gop;
+    // the table, then the I-frames' sums [nq][G]
+    if ((r = res.check(c)) || (r = stage(c, y, w, h, stride, frame_pitch, nframes, q, nq, &dy)) ||
+        (r = res.place(c, size_t(nq) * size_t(G))))
+        return r;
+
+    // the I-frames alone (they are gop frames apart), scattered into the table
+    ie::launch_probe_sizes(probe_args(c, dy, w, h, stride, size_t(gop) * frame_pitch, G, use_rle, 0, nq, res.extra), n,
+                           c->stream);
+    HIPCHK(c, hipGetLastError());
+    // P-frames whose size is a closed form: the vectors of the macroblocks and nothing else
+    const int nmb = (w / 16) * (h / 16);
+    const bool closed = n != 4 || nmb == 0;
+    ie::launch_pframe_probe_scatter(reinterpret_cast<const unsigned long long*>(res.extra),
+                                    reinterpret_cast<unsigned long long*>(res.dbits), nq, nframes, gop, G, closed ? 1 : 0,
+                                    uint64_t(nmb) * 2u * uint64_t(mvec_bits(merange)), c->stream);
+    HIPCHK(c, hipGetLastError());
+
+    if (!closed) {
+        const GopCall g{dy, w, h, stride, frame_pitch, nframes, gop, merange, use_rle, nq, res.dbits};
+        GopPlan pl;
+        if ((r = gop_plan(c, g, 2, &pl))) return r;  // a pair: reconstruction 0, 1
+        r = gop_waves<ie::PgArgs>(
+            c, g, pl, [](int, int, int, int) { return IE_OK; },
+            [&](const ie::PgArgs& a, int, bool, size_t, int gj) { ie::launch_pframe_probe(a, gj, c->stream); });
+        if (r) return r;
+    }
+    return res.finish(c);
+}
+
+extern "C" int ie_probe_gop_rd(ie_ctx* c, const uint8_t* y, int w, int h, size_t stride, size_t frame_pitch, int nframes,
+                               int gop, int merange, int use_rle, int motioncomp, const uint16_t* q, int nq,
+                               uint64_t* bits, uint64_t* sse) {
+    if (!c || !y || !q || !sse) return IE_EINVAL;
+    gop = std::max(1, gop);
+    size_t need = 0;
+    int r = check_gop(c, w, h, stride, frame_pitch, nframes, gop, merange, SIZE_MAX, 0, &need);
+    if (r) return r;
+    if ((r = check_candidates(c, q, nq))) return r;
+    const bool pframes = gop > 1 && nframes > 1;
+    if (pframes && (w % 16 || h % 16))  // ie_decode_gop's rule: no decoded pixels exist to compare with
+        return fail(c, IE_EINVAL, "P-frames decode for W and H multiples of 16 only: there is no decoded video to measure");
+    if (!pframes) return ie_probe_rd(c, y, w, h, stride, frame_pitch, nframes, use_rle, q, nq, bits, sse);
+    if (c->n != 4)
+        // ie_encode_gop writes no microblock records for 8x8 P-frames, ie_decode_gop reads one per
+        // microblock: it parses the following frames' bits as records, or runs out of stream
+        return fail(c, IE_EINVAL, "8x8 P-frame streams do not decode (the encoder writes no records, the decoder reads "
+                                  "one per block): there is no decoded video to measure");
+    HIPCHK(c, hipSetDevice(c->device));
+    Results res{bits, sse, size_t(nq) * size_t(nframes)};
+    const uint8_t* dy;
+    if ((r = res.check(c)) || (r = stage(c, y, w, h, stride, frame_pitch, nframes, q, nq, &dy)) || (r = res.place(c))) return r;
+    unsigned long long* const usse = reinterpret_cast<unsigned long long*>(res.dsse);
+
+    const GopCall g{dy, w, h, stride, frame_pitch, nframes, gop, merange, use_rle, nq, res.dbits};
+    GopPlan pl;
+    if ((r = gop_plan(c, g, 4, &pl))) return r;  // a pair: reconstruction 0, 1, decoded frame 0, 1
+    uint8_t* const dec = c->d_probe_gop + 2 * pl.fpx;
+
+    // the I-frames of `ng` groups from frame f0 under candidates [m0, m0 + nm); the first `store`
+    // of them leave their decoded pixels in their pairs' decoded frame 0
+    const auto iframes = [&](int f0, int ng, int m0, int nm, int store) {
+        const size_t at = size_t(m0) * size_t(nframes) + size_t(f0);
+        ie::ProbeArgs ia = probe_args(c, dy + size_t(f0) * frame_pitch, w, h, stride, size_t(gop) * frame_pitch, ng, use_rle,
+                                      m0, nm, res.dbits ? res.dbits + at : nullptr);
+        ia.out_m = uint64_t(nframes);
+        ia.out_f = uint64_t(gop);
+        ia.dec = dec;
+        ia.f_dec = size_t(pl.chunk) * pl.pair_bytes;
+        ia.m_dec = pl.pair_bytes;
+        ia.dec_frames = store;
+        ie::launch_probe_rd_store(ia, usse + at, c->stream);
+        HIPCHK(c, hipGetLastError());
+        return int(IE_OK);
+    };
+    r = gop_waves<ie::PgRdArgs>(
+        c, g, pl, [&](int f0, int gw, int m0, int nm) { return iframes(f0, gw, m0, nm, gw); },
+        [&](ie::PgRdArgs& a, int j, bool last, size_t at, int gj) {
+            a.dref = dec + size_t((j - 1) & 1) * pl.fpx;  // the decoder never shares: frame 0 is the decoded I-frame
+            a.dec = last ? nullptr : dec + size_t(j & 1) * pl.fpx;
+            a.g_dec = a.g_rec;
+            a.m_dec = a.m_rec;
+            a.motioncomp = motioncomp ? 1 : 0;
+            a.sse = usse + at;
+            ie::launch_pframe_probe_rd(a, gj, c->stream);
+        });
+    if (r) return r;
+    const int G = (nframes + gop - 1) / gop;
+    if (G > pl.Gp && (r = iframes(pl.Gp * gop, 1, 0, nq, 0))) return r;  // a last group of one I-frame: nothing follows it, nothing is stored
+    return res.finish(c);
 }

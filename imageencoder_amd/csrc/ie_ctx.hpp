@@ -237,19 +237,18 @@ struct ie_ctx {
     // every group's reconstructed frames, coefficients, record lengths, tile sums; the wave's
     // position table and the groups' first bits).  The frames' positions in the stream: d_gop_pos.
     iec::Buf<uint8_t> d_gopg;
-    // ie_probe_sizes / ie_probe_rd: the candidate matrices (zig-zag order; pinned, then device:
+    // The probes (ie_capi_probe.cpp): the candidate matrices (zig-zag order; pinned, then device:
     // IE_PROBE_MAX of them), the event after the copy out of the pinned block, the sums when the
-    // results are host memory (ie_probe_rd: bits, then sse, read back together into h_probe_out)
+    // results are host memory (with sse: bits, then sse, read back together into h_probe_out)
     iec::Buf<uint16_t, iec::Mem::Pinned> h_probe_q;
     iec::Buf<uint16_t> d_probe_q;
     iec::Event ev_probe;
     bool probe_recorded = false;
     iec::Buf<uint64_t> d_probe_bits;
     iec::Buf<uint64_t, iec::Mem::Pinned> h_probe_out;
-    // ie_probe_gop: two reconstructed frames per (group, candidate) pair of one wave
+    // the gop probes: the frames of every (group, candidate) pair of one wave (ie_probe_gop: two
+    // reconstructions; ie_probe_gop_rd: two reconstructions, then two decoded frames)
     iec::Buf<uint8_t> d_probe_gop;
-    // ie_probe_gop_rd: four frames per pair -- two reconstructions, two decoded frames
-    iec::Buf<uint8_t> d_probe_gop_rd;
 };
 
 namespace iec {
@@ -427,12 +426,6 @@ int gop_wave_scratch(ie_ctx* c, int w, int h, int gop, int merange, size_t Gw, G
 int launch_gop_wave(ie_ctx* c, const GopWave& W, const uint8_t* wy, int w, int h, size_t stride, size_t frame_pitch,
                     int gw, int nfw, int merange, int use_rle, int mode, uint32_t* dout, uint64_t start_bit,
                     const uint64_t* base_dev, uint64_t* fpos);
-
-// ---- ie_capi_probe.cpp: the candidates of a probe (ie_probe_sizes, ie_probe_rd, ie_probe_gop)
-// nq in [1, IE_PROBE_MAX] and no zero entry, else IE_EINVAL (the message names the matrix)
-int check_candidates(ie_ctx* c, const uint16_t* q, int nq);
-// The candidates in zig-zag order to d_probe_q on the stream, through pinned memory.
-int stage_candidates(ie_ctx* c, const uint16_t* q, int nq);
 
 // ---- ie_capi_decode.cpp: the record parse's chunk plan and scratch (ie_capi_vdec.cpp plans its
 // chunks of frames with them)

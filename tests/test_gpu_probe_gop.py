@@ -12,46 +12,16 @@ mix-up between two candidates' reconstruction buffers changes bits from the seco
 import numpy as np
 import pytest
 
-from imageencoder_amd import IE_EINVAL, IE_ENOQUANT, MODE_EXACT, MODE_FAST, IEError, scale_matrix, synth
-from tests import matrix_sweep as MS
+from imageencoder_amd import IE_EINVAL, MODE_EXACT, MODE_FAST, IEError, scale_matrix, synth
+from tests.probe_common import base as _base
+from tests.probe_common import check_table as _check
+from tests.probe_common import codec, device_table, fresh_context_refuses  # noqa: F401
+from tests.probe_common import gop_bits as _expected
+from tests.probe_common import gop_candidates as _candidates
+from tests.probe_common import gop_contents as _contents
+from tests.probe_common import gop_few as _few
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def codec():
-    from imageencoder_amd import Codec
-    return Codec(0)
-
-
-def _base(n):
-    return MS.by_name(n, "jpeg_like" if n == 4 else "annex_k")
-
-
-def _candidates(n):
-    """The context's own matrix first, the sweep, the base scaled across the budget ladder's range."""
-    qs = [_base(n)] + [q for _, q in MS.sweep(n)] + [scale_matrix(_base(n), p) for p in (25, 59, 336, 1345, 5382)]
-    assert len(qs) <= 64
-    return np.stack(qs)
-
-
-def _few(n):
-    return _candidates(n)[[0, 2, -5, -2, -1]]
-
-
-def _expected(oracle, y, n, qs, gop, merange, rle=True, **layout):
-    return np.stack([oracle.encode_gop(y, n, q, gop, merange, rle=rle, **layout)[2] for q in qs]).astype(np.uint64)
-
-
-def _contents(n, f, h, w):
-    return [("noise", synth.frames("U", w, h, f, seed=31)), ("shift", synth.frames("shiftA", w, h, f, seed=5)),
-            ("flat", synth.frames("flat128", w, h, f)), ("ties", MS.tie_frames(n, _base(n), w, h, f, seed=2))]
-
-
-def _check(got, exp, what):
-    assert got.dtype == np.uint64 and got.shape == exp.shape
-    bad = np.argwhere(got != exp)
-    assert bad.size == 0, (what, "candidate, frame:", bad[:4].tolist(), got[bad[0][0]], exp[bad[0][0]])
 
 
 @pytest.mark.parametrize("rle", [True, False], ids=["rle", "norle"])
@@ -132,7 +102,7 @@ def test_padded_rows_and_frames_host_and_device(codec, oracle):
         dev = torch.full((len(qs) * f,), -1, dtype=torch.int64, device="cuda")
         assert codec.probe_gop(src, w, h, qs, gop, merange, nframes=f, stride=stride, frame_pitch=pitch, out=dev) is dev
         codec.sync()
-        _check(dev.cpu().numpy().view(np.uint64).reshape(len(qs), f), exp, "device bits")
+        _check(device_table(dev, len(qs), f), exp, "device bits")
 
 
 def test_waves_never_change_the_table(codec, oracle, monkeypatch):
@@ -182,14 +152,8 @@ def test_arguments(codec, oracle):
 
 
 def test_fresh_context_has_no_block_size():
-    from imageencoder_amd import Codec
-    c = Codec(0)
-    try:
-        with pytest.raises(IEError) as e:
-            c.probe_gop(np.zeros((2, 16, 16), dtype=np.uint8), 16, 16, np.ones((1, 16), dtype=np.uint16), 2, 4, nframes=2)
-        assert e.value.code == IE_ENOQUANT
-    finally:
-        c.close()
+    fresh_context_refuses(
+        lambda c: c.probe_gop(np.zeros((2, 16, 16), dtype=np.uint8), 16, 16, np.ones((1, 16), dtype=np.uint16), 2, 4, nframes=2))
 
 
 def test_rows_equal_the_librarys_own_encodes(codec):

@@ -25,36 +25,16 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from imageencoder_amd import IE_EINVAL, IE_ENOQUANT, MODE_EXACT, MODE_FAST, IEError, scale_matrix, synth
-from tests import matrix_sweep as MS
+from imageencoder_amd import IE_EINVAL, MODE_EXACT, MODE_FAST, IEError, scale_matrix, synth
+from tests.probe_common import base as _base
+from tests.probe_common import check_table as _check
+from tests.probe_common import codec, device_table, fresh_context_refuses  # noqa: F401
+from tests.probe_common import gop_bits as _bits
+from tests.probe_common import gop_candidates as _candidates
+from tests.probe_common import gop_contents as _contents
+from tests.probe_common import gop_few as _few
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def codec():
-    from imageencoder_amd import Codec
-    return Codec(0)
-
-
-def _base(n):
-    return MS.by_name(n, "jpeg_like" if n == 4 else "annex_k")
-
-
-def _candidates(n):
-    """The context's own matrix first, the sweep, the base scaled across the budget ladder's range."""
-    qs = [_base(n)] + [q for _, q in MS.sweep(n)] + [scale_matrix(_base(n), p) for p in (25, 59, 336, 1345, 5382)]
-    assert len(qs) <= 64
-    return np.stack(qs)
-
-
-def _few(n):
-    return _candidates(n)[[0, 2, -5, -2, -1]]
-
-
-def _contents(n, f, h, w):
-    return [("noise", synth.frames("U", w, h, f, seed=31)), ("shift", synth.frames("shiftA", w, h, f, seed=5)),
-            ("flat", synth.frames("flat128", w, h, f)), ("ties", MS.tie_frames(n, _base(n), w, h, f, seed=2))]
 
 
 def _decoded(oracle, y, n, q, gop, merange, rle, motioncomp):
@@ -71,16 +51,6 @@ def _sse(dec, y):
 
 def _truth(oracle, y, n, qs, gop, merange, rle=True, motioncomp=True):
     return np.stack([_sse(_decoded(oracle, y, n, q, gop, merange, rle, motioncomp), y) for q in qs])
-
-
-def _bits(oracle, y, n, qs, gop, merange, rle=True, **layout):
-    return np.stack([oracle.encode_gop(y, n, q, gop, merange, rle=rle, **layout)[2] for q in qs]).astype(np.uint64)
-
-
-def _check(got, exp, what):
-    assert got.dtype == np.uint64 and got.shape == exp.shape
-    bad = np.argwhere(got != exp)
-    assert bad.size == 0, (what, "candidate, frame:", bad[:4].tolist(), got[bad[0][0]], exp[bad[0][0]])
 
 
 @pytest.mark.parametrize("motioncomp", [True, False], ids=["mc", "nomc"])
@@ -207,12 +177,12 @@ def test_padded_rows_and_frames_host_and_device(codec, oracle):
         pair = (db, ds)
         assert codec.probe_gop_rd(src, w, h, qs, gop, merange, out=pair, **lay) is pair
         codec.sync()
-        _check(ds.cpu().numpy().view(np.uint64).reshape(nq, f), exp, "device sse")
-        _check(db.cpu().numpy().view(np.uint64).reshape(nq, f), exp_bits, "device bits")
+        _check(device_table(ds, nq, f), exp, "device sse")
+        _check(device_table(db, nq, f), exp_bits, "device bits")
         ds.fill_(-1)
         codec.probe_gop_rd(src, w, h, qs, gop, merange, out=(None, ds), **lay)  # bits = NULL, device
         codec.sync()
-        _check(ds.cpu().numpy().view(np.uint64).reshape(nq, f), exp, "device sse alone")
+        _check(device_table(ds, nq, f), exp, "device sse alone")
         only = np.zeros((nq, f), dtype=np.uint64)  # bits = NULL, host
         codec._chk(codec.L.ie_probe_gop_rd(codec.h, src.ctypes.data if src is buf else src.data_ptr(), w, h, stride, pitch, f,
                                            gop, merange, 1, 1, np.ascontiguousarray(qs).ctypes.data, nq, None,
@@ -304,14 +274,8 @@ def test_arguments(codec, oracle):
 
 
 def test_fresh_context_has_no_block_size():
-    from imageencoder_amd import Codec
-    c = Codec(0)
-    try:
-        with pytest.raises(IEError) as e:
-            c.probe_gop_rd(np.zeros((2, 16, 16), dtype=np.uint8), 16, 16, np.ones((1, 16), dtype=np.uint16), 2, 4, nframes=2)
-        assert e.value.code == IE_ENOQUANT
-    finally:
-        c.close()
+    fresh_context_refuses(
+        lambda c: c.probe_gop_rd(np.zeros((2, 16, 16), dtype=np.uint8), 16, 16, np.ones((1, 16), dtype=np.uint16), 2, 4, nframes=2))
 
 
 def test_probe_leaves_the_context_untouched(codec):
@@ -331,3 +295,71 @@ def test_probe_leaves_the_context_untouched(codec):
     after = state()
     assert before == after
     assert bits[0].tolist() == before[1]  # candidate 0 is the context's own matrix
+
+
+# ---- the four probes on one context.  32 x 16 x 5 (two macroblocks), gop 2: two groups with a
+# P-frame, then a group of one I-frame; three candidates
+_SMALL = dict(w=32, h=16, f=5, gop=2, merange=2)
+
+
+def _small_frames():
+    return synth.frames("shiftA", _SMALL["w"], _SMALL["h"], _SMALL["f"], seed=23)
+
+
+def test_interleaved_asynchronous_calls(codec, monkeypatch):
+    """probe_sizes, probe_rd, probe_gop and probe_gop_rd back to back into device results, one
+    synchronisation after the last: they share the staged candidates, the sums of probe_gop's
+    I-frames and the pairs' scratch, in stream order.  IE_PROBE_GOP_MAX = 2: candidate chunks of
+    2 + 1, one group per wave.  Every table equals what the same call returns alone with host
+    results.  Then 8x8 blocks (probe_gop's closed form; probe_gop_rd refuses them)."""
+    import torch
+    w, h, f, gop, merange = (_SMALL[k] for k in ("w", "h", "f", "gop", "merange"))
+    dy = torch.from_numpy(_small_frames()).cuda()
+    monkeypatch.setenv("IE_PROBE_GOP_MAX", "2")
+    for n in (4, 8):
+        codec.set_quant(_base(n), n)
+        qs = _candidates(n)[[0, 2, -1]]
+        nq = len(qs)
+        calls = [("probe_sizes", False, lambda **o: codec.probe_sizes(dy, w, h, qs, nframes=f, **o)),
+                 ("probe_rd", True, lambda **o: codec.probe_rd(dy, w, h, qs, nframes=f, **o)),
+                 ("probe_gop", False, lambda **o: codec.probe_gop(dy, w, h, qs, gop, merange, nframes=f, **o))]
+        if n == 4:
+            calls.append(("probe_gop_rd", True, lambda **o: codec.probe_gop_rd(dy, w, h, qs, gop, merange, nframes=f, **o)))
+        alone = [call() for _, _, call in calls]
+
+        def table():
+            return torch.full((nq * f,), -1, dtype=torch.int64, device="cuda")
+
+        outs = [(table(), table()) if rd else table() for _, rd, _ in calls]
+        for (_, _, call), out in zip(calls, outs):
+            assert call(out=out) is out
+        codec.sync()
+        for (name, rd, _), ref, out in zip(calls, alone, outs):
+            for k, (r, o) in enumerate(zip(ref, out) if rd else [(ref, out)]):
+                _check(device_table(o, nq, f), r, f"{name} n={n} result {k}")
+    codec.set_quant(_base(4), 4)
+
+
+@pytest.mark.parametrize("off", [0, 1], ids=["aligned", "ptr+1"])
+def test_frame_pitch_2_mod_4(codec, off):
+    """gop 2 and a frame pitch of w * h + 2: the I-frames of the groups lie a multiple of 4 bytes
+    apart though the frames do not, so their rows may be read with 4-byte loads; from a pointer one
+    byte further on they are read byte by byte.  Both give the tables of the packed frames."""
+    import torch
+    n, w, h, f, gop, merange = 4, *(_SMALL[k] for k in ("w", "h", "f", "gop", "merange"))
+    pitch = w * h + 2
+    y = _small_frames()
+    buf = np.full(off + f * pitch, 0xA5, dtype=np.uint8)
+    for k in range(f):
+        buf[off + k * pitch: off + k * pitch + w * h] = y[k].ravel()
+    dbuf = torch.from_numpy(buf).cuda()
+    assert dbuf.data_ptr() % 4 == 0 and pitch % 4 == 2 and (gop * pitch) % 4 == 0
+    packed = torch.from_numpy(y).cuda()
+    codec.set_quant(_base(n), n)
+    qs = _candidates(n)[[0, 2, -1]]
+    _check(codec.probe_gop(dbuf[off:], w, h, qs, gop, merange, nframes=f, frame_pitch=pitch),
+           codec.probe_gop(packed, w, h, qs, gop, merange, nframes=f), "probe_gop")
+    got = codec.probe_gop_rd(dbuf[off:], w, h, qs, gop, merange, nframes=f, frame_pitch=pitch)
+    exp = codec.probe_gop_rd(packed, w, h, qs, gop, merange, nframes=f)
+    _check(got[0], exp[0], "probe_gop_rd bits")
+    _check(got[1], exp[1], "probe_gop_rd sse")

@@ -15,18 +15,13 @@ at most 512, 2048 x 1032 is 516 tiles), so a workgroup flushes at a frame change
 import numpy as np
 import pytest
 
-from imageencoder_amd import IE_EINVAL, IE_ENOQUANT, IEError, scale_matrix, stream_bound
+from imageencoder_amd import IE_EINVAL, IEError, scale_matrix, stream_bound
 from tests import crafted_streams as CS
 from tests import matrix_sweep as MS
 from tests import oracle_lib as O
+from tests.probe_common import codec, device_table, fresh_context_refuses  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def codec():
-    from imageencoder_amd import Codec
-    return Codec(0)
 
 
 def _base(n):
@@ -194,14 +189,7 @@ def test_candidate_count_boundaries(codec):
 
 
 def test_fresh_context_has_no_block_size():
-    from imageencoder_amd import Codec
-    c = Codec(0)
-    try:
-        with pytest.raises(IEError) as e:
-            c.probe_rd(np.zeros((8, 8), dtype=np.uint8), 8, 8, np.ones((1, 16), dtype=np.uint16))
-        assert e.value.code == IE_ENOQUANT
-    finally:
-        c.close()
+    fresh_context_refuses(lambda c: c.probe_rd(np.zeros((8, 8), dtype=np.uint8), 8, 8, np.ones((1, 16), dtype=np.uint16)))
 
 
 @pytest.mark.parametrize("n", [4, 8])
@@ -233,12 +221,12 @@ def test_null_bits_device_results_and_mixed_results(codec, n):
     out = codec.probe_rd(dy, w, h, qs, nframes=f, out=(db, ds))
     assert out[0] is db and out[1] is ds
     codec.sync()
-    np.testing.assert_array_equal(db.cpu().numpy().view(np.uint64).reshape(nq, f), eb)
-    np.testing.assert_array_equal(ds.cpu().numpy().view(np.uint64).reshape(nq, f), es)
+    np.testing.assert_array_equal(device_table(db, nq, f), eb)
+    np.testing.assert_array_equal(device_table(ds, nq, f), es)
     ds.fill_(-1)
     codec.probe_rd(dy, w, h, qs, nframes=f, out=(None, ds))
     codec.sync()
-    np.testing.assert_array_equal(ds.cpu().numpy().view(np.uint64).reshape(nq, f), es)
+    np.testing.assert_array_equal(device_table(ds, nq, f), es)
     # host bits with device sse, and the reverse
     for b, s in ((bits.ctypes.data_as(u64p), C.cast(C.c_void_p(ds.data_ptr()), u64p)),
                  (C.cast(C.c_void_p(db.data_ptr()), u64p), sse.ctypes.data_as(u64p))):

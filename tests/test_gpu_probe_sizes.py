@@ -12,20 +12,12 @@ division or rounding shows.  Candidates: every matrix of the sweep in one call."
 import numpy as np
 import pytest
 
-from imageencoder_amd import IE_EINVAL, IE_ENOQUANT, MODE_EXACT, MODE_FAST, IEError, stream_bound, synth
+from imageencoder_amd import IE_EINVAL, MODE_EXACT, MODE_FAST, IEError, stream_bound, synth
 from tests import matrix_sweep as MS
+from tests.probe_common import base as _base
+from tests.probe_common import codec, device_table, fresh_context_refuses  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def codec():
-    from imageencoder_amd import Codec
-    return Codec(0)
-
-
-def _base(n):
-    return MS.by_name(n, "jpeg_like" if n == 4 else "annex_k")
 
 
 def _candidates(n):
@@ -110,8 +102,7 @@ def test_frames_with_padded_rows_and_frames(codec, oracle, n, pad):
             dev = torch.full((len(qs) * f,), -1, dtype=torch.int64, device="cuda")
             assert codec.probe_sizes(src, w, h, qs, nframes=f, stride=stride, frame_pitch=pitch, out=dev) is dev
             codec.sync()
-            np.testing.assert_array_equal(dev.cpu().numpy().view(np.uint64).reshape(len(qs), f), exp,
-                                          err_msg=f"{kind} device bits")
+            np.testing.assert_array_equal(device_table(dev, len(qs), f), exp, err_msg=f"{kind} device bits")
 
 
 @pytest.mark.parametrize("n", [4, 8])
@@ -150,14 +141,7 @@ def test_candidate_count_boundaries(codec, oracle):
 
 
 def test_fresh_context_has_no_block_size():
-    from imageencoder_amd import Codec
-    c = Codec(0)
-    try:
-        with pytest.raises(IEError) as e:
-            c.probe_sizes(np.zeros((8, 8), dtype=np.uint8), 8, 8, np.ones((1, 16), dtype=np.uint16))
-        assert e.value.code == IE_ENOQUANT
-    finally:
-        c.close()
+    fresh_context_refuses(lambda c: c.probe_sizes(np.zeros((8, 8), dtype=np.uint8), 8, 8, np.ones((1, 16), dtype=np.uint16)))
 
 
 @pytest.mark.parametrize("n", [4, 8])
