@@ -511,9 +511,16 @@ __global__ __launch_bounds__(kMbTPB) void pf_mvcopy_kernel(const uint8_t* in, ui
     if (dstart) start_bit = min(*dstart, nbits);
     const uint64_t p = start_bit + uint64_t(mb) * 2u * uint32_t(mv);
     if (p + 2u * uint32_t(mv) > nbits) return;  // (a truncated stream: the host reports it)
-    uint64_t win = 0;  // 64 stream bits from byte p/8 (2*mv <= 32 bits + 7 bits of offset)
+    // 64 stream bits from byte p/8 (2*mv <= 32 bits + 7 bits of offset); bytes past the stream's
+    // last one read as 0 (a caller's device stream read in place ends there: the vectors of the last
+    // macroblock may lie in its last bytes)
+    const uint64_t nbytes = (nbits + 7) >> 3;
+    uint64_t win = 0;
 #pragma unroll
-    for (int k = 0; k < 8; k++) win = (win << 8) | in[(p >> 3) + k];
+    for (int k = 0; k < 8; k++) {
+        const uint64_t i = (p >> 3) + uint64_t(k);
+        win = (win << 8) | (i < nbytes ? in[i] : uint8_t(0));
+    }
     const uint32_t s = uint32_t(p & 7u);
     const uint32_t rx = uint32_t(win >> (64 - s - uint32_t(mv))) & ((1u << mv) - 1u);
     const uint32_t ry = uint32_t(win >> (64 - s - 2u * uint32_t(mv))) & ((1u << mv) - 1u);

@@ -387,34 +387,3 @@ def by_family(family: str) -> list[Entry]:
 
 def by_name(name: str) -> Entry:
     return next(e for e in entries() if e.name == name)
-
-
-# ------------------------------------------------------------------------------ a P-frame video
-GOP_CASE = dict(n=4, w=64, h=48, frames=3, gop=3, merange=8, rle=True, mat="ref")
-
-
-def gop_case() -> bytes:
-    """A video file, frames I P P, whose I-frame and P-frame records use bl = 0 and bl = 15 (small
-    values in wide fields next to full-range ones) and whose vectors span [-merange, merange]."""
-    g = GOP_CASE
-    rng = _rng("gop_case")
-    n, nn = g["n"], g["n"] * g["n"]
-    nb = (g["w"] // n) * (g["h"] // n)
-    nmb = (g["w"] // 16) * (g["h"] // 16)
-    frames = []
-    for f in range(g["frames"]):
-        recs = []
-        for i in range(nb):
-            k = (i + f) % 4
-            if k == 0:
-                recs.append((0, 0, []))
-            elif k == 1:  # bl = 15 fields holding small values
-                lw = int(rng.integers(0, nn + 1))
-                recs.append((15, lw, [int(v) for v in rng.integers(-6, 7, size=lw)]))
-            elif k == 2:
-                recs.append(_rec(rng, n, True, 15, int(rng.integers(0, nn + 1)), edges_at=i))
-            else:
-                recs.append(_rec(rng, n, True, int(rng.integers(1, 8)), int(rng.integers(0, nn + 1))))
-        mv = None if f % g["gop"] == 0 else [(int(a), int(b)) for a, b in rng.integers(-g["merange"], g["merange"] + 1, size=(nmb, 2))]
-        frames.append((mv, recs))
-    return S.pack_video(frames, n, matrix(n, g["mat"]), True, g["w"], g["h"], g["gop"], g["merange"])

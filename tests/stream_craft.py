@@ -83,20 +83,44 @@ def pack(records, n: int, q, rle, w: int, h: int):
     return _finish(parts), pos
 
 
-def pack_video(frames, n: int, q, rle, w: int, h: int, gop: int, merange: int):
+def mvec_bits(merange: int) -> int:
+    """The width of a motion vector component: the signed value `merange`'s (1 bit for 0)."""
+    return int(merange).bit_length() + 1
+
+
+def pack_video(frames, n: int, q, rle, w: int, h: int, gop: int, merange: int, positions: bool = False):
     """A video file.  frames: one (mvecs, records) per frame; mvecs is None for an I-frame, else
     one (vx, vy) per 16x16 macroblock, each stored in the bit length of merange plus a sign bit
-    as the encoder sizes it (the width of the signed value `merange`)."""
-    mv = int(merange).bit_length() + 1
+    as the encoder sizes it (the width of the signed value `merange`): any value of that field is
+    valid, not only those inside [-merange, merange].
+
+    With positions the result is (bytes, pos): pos[f] = dict(start = the frame's first bit, vec =
+    the first bit of every macroblock's vector pair ([] for an I-frame), rec = the first bit of
+    every record, end = the frame's end bit, which is the next frame's first)."""
+    mv = mvec_bits(merange)
+    lo, hi = -(1 << (mv - 1)), (1 << (mv - 1)) - 1
     parts = [header_bits(n, q, rle, w, h, video=(len(frames), gop, merange))]
+    at = int(parts[0].size)
+    pos = []
     for f, (mvecs, records) in enumerate(frames):
         assert (mvecs is None) == (f % gop == 0)
         assert len(records) == (w // n) * (h // n)
+        fp = dict(start=at, vec=[], rec=[])
         if mvecs is not None:
             assert len(mvecs) == (w // 16) * (h // 16)
-            parts.append(_field(np.asarray(mvecs, dtype=np.int64).ravel(), mv))
-        parts += [record_bits(r, n, rle) for r in records]
-    return _finish(parts)
+            v = np.asarray(mvecs, dtype=np.int64).reshape(-1, 2)
+            assert v.size == 0 or (lo <= v.min() and v.max() <= hi), (f, mv)
+            parts.append(_field(v.ravel(), mv))
+            fp["vec"] = [at + 2 * mv * k for k in range(len(mvecs))]
+            at += 2 * mv * len(mvecs)
+        for r in records:
+            b = record_bits(r, n, rle)
+            parts.append(b)
+            fp["rec"].append(at)
+            at += int(b.size)
+        fp["end"] = at
+        pos.append(fp)
+    return (_finish(parts), pos) if positions else _finish(parts)
 
 
 class _Reader:
@@ -141,3 +165,37 @@ def parse(data: bytes, n: int):
         records.append((bl, lw, [int(v) for v in vals]))
         pos.append(rd.pos)
     return records, q.astype(np.uint16), rle, w, h, pos
+
+
+def parse_video(data: bytes, n: int):
+    """The serial parse of a video file written without the Huffman pass, the twin of pack_video.
+    Returns (frames, q, rle, w, h, gop, merange, positions), frames and positions as pack_video
+    takes and returns them."""
+    rd = _Reader(data)
+    assert rd.get(1) == 0, "Huffman-coded file"
+    qb = rd.get(5)
+    q = rd.fields(n * n, qb)
+    rle = bool(rd.get(1))
+    w, h = rd.get(15), rd.get(15)
+    nframes, gop, merange = rd.get(15), max(1, rd.get(15)), rd.get(15)
+    mv = mvec_bits(merange)
+    nmb = (w // 16) * (h // 16)
+    frames, pos = [], []
+    for f in range(nframes):
+        fp = dict(start=rd.pos, vec=[], rec=[])
+        mvecs = None
+        if f % gop:
+            fp["vec"] = [rd.pos + 2 * mv * k for k in range(nmb)]
+            v = _signed(rd.fields(2 * nmb, mv), mv).reshape(nmb, 2)
+            mvecs = [(int(a), int(b)) for a, b in v]
+        records = []
+        for _ in range((w // n) * (h // n)):
+            fp["rec"].append(rd.pos)
+            bl = rd.get(4)
+            lw = rd.get(bl) if rle else n * n
+            assert lw <= n * n, "value count beyond the block"
+            records.append((bl, lw, [int(x) for x in _signed(rd.fields(lw, bl), bl)]))
+        fp["end"] = rd.pos
+        frames.append((mvecs, records))
+        pos.append(fp)
+    return frames, q.astype(np.uint16), rle, w, h, gop, merange, pos

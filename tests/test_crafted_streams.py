@@ -201,7 +201,14 @@ def test_oracle_decodes_crafted_as_reference(oracle, m):
 
 
 def test_oracle_decodes_gop_case(oracle):
-    """The P-frame video of the GPU test parses to its end in the oracle (pixels are compared on the GPU)."""
-    g = CS.GOP_CASE
-    out = oracle.decode_video_gop(CS.gop_case(), g["n"])
-    assert len(out) == g["frames"] * (g["w"] * g["h"] * 3 // 2)
+    """The P-frame video of the GPU test (the entry gop_case of tests/crafted_videos.py), pinned: the
+    oracle's decode, motion compensation on and off, has the md5 of the REFERENCE's own decode
+    (manifest_crafted_video.json)."""
+    from tests import crafted_videos as CV
+    e = CV.by_name("gop_case")
+    m = next(m for m in json.load(open(os.path.join(O.GOLDEN, "manifest_crafted_video.json"))) if m["name"] == e.name)
+    assert _md5(e.data) == m["md5"], "the table no longer builds the file the reference decoded"
+    for mc in (1, 0):
+        out = oracle.decode_video_gop(e.data, e.n, bool(mc))
+        assert len(out) == e.frames * (e.w * e.h * 3 // 2)
+        assert _md5(out) == m[f"dec{mc}_md5"], mc

@@ -9,7 +9,8 @@ Every entry of the table goes through
 and must equal the oracle's pixels (np.array_equal, the first differing block reported) and the
 md5 of the REFERENCE's own decode (tests/golden/manifest_crafted.json).  The oracle's pixels are
 computed once per entry and shared.  A P-frame video with bl = 0 and bl = 15 records in its I- and
-P-frames goes through ie_decode_gop against the oracle's decode_video_gop.
+P-frames (the entry gop_case of tests/crafted_videos.py, whose table tests/test_gpu_crafted_videos.py
+runs in full) goes through ie_decode_gop against the oracle's decode_video_gop.
 """
 import hashlib
 import json
@@ -146,13 +147,14 @@ def test_gop_with_zero_and_full_width_records(motioncomp):
     """I P P, 64x48, records of bl = 0 and bl = 15 in every frame: ie_decode_gop (through the file
     decoder) == the oracle's decode_video_gop.  (The record reader is the one the image entries pin
     against the reference.)"""
-    g = CS.GOP_CASE
-    data = CS.gop_case()
-    exp = O.load().decode_video_gop(data, g["n"], motioncomp=motioncomp)
-    c = _codec(g["n"])
-    got, (w, h, f) = c.decode_video_file(data, g["n"])
-    assert (w, h, f) == (g["w"], g["h"], g["frames"])
+    from tests import crafted_videos as CV
+    e = CV.by_name("gop_case")
+    data = e.data
+    exp = O.load().decode_video_gop(data, e.n, motioncomp=motioncomp)
+    c = _codec(e.n)
+    got, (w, h, f) = c.decode_video_file(data, e.n)
+    assert (w, h, f) == (e.w, e.h, e.frames)
     got = got.reshape(f, h * w * 3 // 2)
     ref = np.frombuffer(exp, dtype=np.uint8).reshape(f, h * w * 3 // 2)
     for k in range(f):
-        assert np.array_equal(got[k], ref[k]), f"frame {k} ({'I' if k % g['gop'] == 0 else 'P'})"
+        assert np.array_equal(got[k], ref[k]), f"frame {k} ({'I' if k % e.gop == 0 else 'P'})"
