@@ -33,7 +33,8 @@ int pack(ie_ctx* c, const uint8_t* bytes, size_t n, const uint32_t* code, const 
         if (reinterpret_cast<uintptr_t>(out) % 4) return fail(c, IE_EINVAL, "device output must be 4-byte aligned");
         dout = reinterpret_cast<uint32_t*>(out);
     } else {
-        if ((r = c->d_out.reserve(c, need_bytes - size_t(w0) * 4))) return r;
+        // (at least the staged word: codes of no bits from a word boundary need no output at all)
+        if ((r = c->d_out.reserve(c, std::max<size_t>(need_bytes - size_t(w0) * 4, 4)))) return r;
         uint8_t word[4] = {0, 0, 0, 0};
         for (int e = 0; e < 4 && size_t(w0) * 4 + e < out_cap; e++) word[e] = out[size_t(w0) * 4 + e];
         HIPCHK(c, hipMemcpyAsync(c->d_out, word, 4, hipMemcpyHostToDevice, c->stream));

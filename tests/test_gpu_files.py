@@ -11,6 +11,7 @@ import pytest
 
 from imageencoder_amd import MODE_EXACT, MODE_FAST, synth
 from tests import oracle_lib as O
+from tests.huffman_inputs import pack_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -205,10 +206,7 @@ def test_huffman_pack_codes(codec):
     for start in (0, 5, 77):
         out = np.zeros(start // 8 + 4 * data.size + 64, np.uint8)
         end = codec.huffman_pack(data, code, length, out, start)
-        ref = []
-        for b in data:
-            l = int(length[b])
-            ref.extend((int(code[b]) >> (l - 1 - k)) & 1 for k in range(l))
+        ref, _ = pack_bits(data, code, length, start)
         assert end == start + len(ref)
         bits = np.unpackbits(out)
         assert np.array_equal(bits[start:end], np.array(ref, np.uint8))
